@@ -33,6 +33,17 @@ ONNG-style out/in edge selection), exact ground truth with the HIP linear
 search, and an epsilon sweep to the smallest epsilon with recall@10 >= 0.95.
 Timing: barrier + synchronize on both sides of exactly K steps, max over
 ranks, rank 0 prints one JSON line.
+
+A run without `--full` (exact and qg modes) does that and no more: setup,
+warm-up, the K timed steps, the line (metric, value, ms_per_step, config,
+sweep).  `--full` adds everything measured or checked beside it, each with
+launches or processes of its own: the exact scan's timing, per-launch kernel
+time and the roofline, single-query latency, the CPU baseline with the oracle
+parity sample, the reference fixture check, and the anng / capi / qg / c3
+(one GPU) or shard (several ranks) lines.  `--dump-outputs DIR` writes the
+last timed step's results as DIR/{ids,distances,counts}.npy; data, queries
+and seeds are fixed, so two builds run with the same arguments compare
+output for output.
 """
 import argparse
 import ctypes
@@ -321,6 +332,14 @@ def main():
                          "'shard' key; auto = on for the default C2 run with more than one rank")
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps: the exact scan's own timing, per-launch kernel time and roofline, "
+                         "single-query latency, the CPU baseline with its oracle parity sample, and the lines "
+                         "measured beside the headline (anng, capi, qg, c3; shard with more than one rank).  Without "
+                         "it the exact and qg modes set up, warm up, time --steps steps and print the line")
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                    help="after the timed steps: write the last timed step's results (ids, distances, counts; what "
+                         "the caller of the search receives) as DIR/<name>.npy")
     ap.add_argument("--mode", choices=["exact", "qg", "shard", "capi"], default="exact")
     ap.add_argument("--threads", type=int, default=128,
                     help="C-API lines: concurrent callers T (runs at 1, T and 2T threads; the serving grid has one "
@@ -479,8 +498,9 @@ def main():
     anng_check = None
     capi_dir = None
     capi_tmp = False
-    if (args.graph == "anng" and args.mode == "exact" and world == 1 and not args.pmc_launches and N == 1_000_000
-            and D == 128 and args.anng_batch == 200 and (args.capi_line == "on" or args.capi_line == "auto")):
+    if (args.full and args.graph == "anng" and args.mode == "exact" and world == 1 and not args.pmc_launches
+            and N == 1_000_000 and D == 128 and args.anng_batch == 200
+            and (args.capi_line == "on" or args.capi_line == "auto")):
         # the C-API line opens the index this run saves (ngt_save_index) from disk
         import tempfile
         if not args.anng_dir:
@@ -531,7 +551,7 @@ def main():
     gt = gt_i.cpu().numpy()
     log("ground truth in %.1f s" % (time.time() - t0))
     scan = None
-    if not shard and not qgm:
+    if args.full and not shard and not qgm:
         # the exact scan itself as a search method (recall 1.0): the batch
         # linear search timed on the same resident queries
         sms = []
@@ -708,6 +728,36 @@ def main():
                           "launches_before": len(sweep), "kernel_ms_last": ix.last_search_kernel_ms()}),
               file=result_out, flush=True)
         return
+    graph = ("kNN%d out%d in%d max%d" % (args.knn, args.out_deg, args.in_deg, args.max_deg) if args.graph == "knn"
+             else "ANNG E%d (ngt_create_index on the device)" % args.anng_edges
+             + ("" if args.anng_batch == 200 else ", batchSizeForCreation %d" % args.anng_batch))
+
+    def names():
+        if args.mode == "exact" and not c3 and N > 2_000_000:
+            metric_name = "QPS at recall@10=0.95, %d x %d-d float L2 on one GPU (C4's index as one graph)" % (N, D)
+            workload = ("C4 on one GPU: %d x %d float L2, ONE device-built ANNG over all objects (not shards), "
+                        "%d queries/step, k=%d" % (N, D, NQ, K))
+        elif args.mode == "exact" and not c3:
+            metric_name = HEADLINE
+            workload = "C2: %d x %d float L2 graph search, %d queries/step/GPU, k=%d" % (N, D, NQ, K)
+        elif args.mode == "exact":
+            metric_name = "QPS at recall@10=0.95, 1M x 960-d float cosine; achieved HBM GB/s vs peak"
+            workload = "C3: %d x %d float cosine graph search, %d queries/step/GPU, k=%d" % (N, D, NQ, K)
+        elif args.mode == "qg":
+            metric_name = "QPS at recall@10=0.95, %d x %d-d NGTQG quantized graph (L2); achieved HBM GB/s" % (N, D)
+            workload = "C5 shape per GPU: %d x %d NGTQG (dsub=1, M=%d, 16 centroids), result_expansion %g, " \
+                       "%d queries/step/GPU, k=%d" % (N, D, D, args.expansion, NQ, K)
+        elif qgm:
+            metric_name = "QPS at recall@10=0.95, %d x %d-d NGTQG sharded over %d GPUs" % (N * world, D, world)
+            workload = "C5 form: %d objects per GPU shard (NGTQG dsub=1, M=%d, result_expansion %g), %d shards, " \
+                       "%d queries/step over all shards, k=%d, one packed RCCL all-gather of per-shard top-k + " \
+                       "device merge" % (N, D, args.expansion, world, NQ, K)
+        else:
+            metric_name = "QPS at recall@10=0.95, %d x %d-d float L2 sharded over %d GPUs" % (N * world, D, world)
+            workload = "C4 form: %d objects per GPU shard, %d shards, %d queries/step over all shards, k=%d, " \
+                       "one packed RCCL all-gather of per-shard top-k + device merge" % (N, world, NQ, K)
+        return metric_name, workload
+
     ns_timed = 1 if shard else max(1, args.streams)
     for i in range(max(args.warmup, ns_timed)):
         run(chosen, i % ns_timed)
@@ -723,6 +773,65 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if dist is not None:
+        t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        elapsed = float(t.item())
+    # replicas: every rank searched its own batch; shard: every rank searched
+    # the same batch on its part of one index
+    qps = NQ * (1 if shard else world) * args.steps / elapsed
+    filtered = (not qgm) and ix.last_search_filtered()
+    if args.dump_outputs and rank == 0:
+        # what the last timed step returned: it ran on stream (steps - 1) % ns_timed
+        oi, od, on, _ = bufs[(args.steps - 1) % ns_timed]
+        dump_outputs(args.dump_outputs, oi.cpu().numpy().view(np.uint32), od.cpu().numpy(), on.cpu().numpy())
+    head = None
+    if rank == 0:
+        metric_name, workload = names()
+        head = {
+            "metric": metric_name,
+            "value": qps,
+            "unit": "queries/s",
+            "n_gpus": n_ranks,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": elapsed / args.steps * 1e3,
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "f32" if not qgm else "u4-adc/u8-lut/f32-rerank",
+            "data": "synthetic (splitmix64 U[0,1), seed 0x4E4754)",
+            "config": {"workload": workload,
+                       "recall_at_10": rec, "epsilon": chosen,
+                       "edge_size": ("all" if args.edge_size == 0 else
+                                     "%d (sc.edgeSize %d; the prf's EdgeSizeForSearch %d)" % (
+                                         es_resolved, args.edge_size, es_prop)),
+                       "graph": graph,
+                       "seeds": ("getSeedsFromTree (DVP tree leaf, seed size %d)" % args.seed_size
+                                 if args.seeds == "tree" else "getRandomSeeds (%d)" % args.seed_size),
+                       "sweep_kernel_ms_cap": SWEEP_KERNEL_MS_CAP,
+                       "visited_set": ("hbm-epochs, every evaluated id (accepted-only and the LDS filter are "
+                                       "off for rows over 1 KiB)" if dp * 4 > 1024 and args.visited in (-1, -2) else
+                                       {-2: "hbm-epochs+lds-filter, accepted ids only",
+                                        -1: "hbm-epochs+lds-filter"}.get(args.visited, "lds-hash")),
+                       "parallelism": ("shards x%d" % world) if shard else ("replicas x%d" % world),
+                       "distance_filter": ("1-byte filter copy (lower bound rejects neighbours outside the "
+                                           "exploration radius; exact f32 rows for the rest)" if filtered else "none"),
+                       "streams": ns_timed},
+        }
+        if qgm:
+            head["config"]["result_expansion"] = args.expansion
+        if build_s is not None:
+            head["config"]["graph_build_s"] = build_s
+        if anng_check is not None:
+            head["config"]["construction_check"] = anng_check
+    if not args.full:
+        # a plain run ends here: the headline figure and the setup it came from
+        if rank == 0:
+            print(json.dumps(dict(head, sweep=sweep)), file=result_out, flush=True)
+        if dist is not None:
+            dist.destroy_process_group()
+        return
     stream_ms = {}
     for n in stream_ab:
         # EXPERIMENT (not the line's value): the same steps alternating over n streams
@@ -742,15 +851,7 @@ def main():
         run(chosen)
         torch.cuda.synchronize()
         kms.append(ix.last_search_kernel_ms())
-    filtered = (not qgm) and ix.last_search_filtered()
     budget = 0 if qgm else ix.last_search_budget()
-    if dist is not None:
-        t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed = float(t.item())
-    # replicas: every rank searched its own batch; shard: every rank searched
-    # the same batch on its part of one index
-    qps = NQ * (1 if shard else world) * args.steps / elapsed
 
     c = cnt.cpu().numpy().astype(np.float64)
     c_timed = c
@@ -780,9 +881,6 @@ def main():
         log("lookahead form %d: %.0f speculative expansions discarded/query (%.0f committed)" % (
             la_form, c[:, 3].mean(), ne.mean()))
     kernel_ms = float(np.mean(kms)) if kms else float("nan")
-    graph = ("kNN%d out%d in%d max%d" % (args.knn, args.out_deg, args.in_deg, args.max_deg) if args.graph == "knn"
-             else "ANNG E%d (ngt_create_index on the device)" % args.anng_edges
-             + ("" if args.anng_batch == 200 else ", batchSizeForCreation %d" % args.anng_batch))
     if qgm:
         # B(q) = sum_exp ceil(deg/16)*16*(M/2) + deg*4 + (seeds + k*expansion)*Dp*4  
         me = (D + 1) // 2 * 2
@@ -913,61 +1011,9 @@ def main():
             shutil.rmtree(capi_dir, ignore_errors=True)
 
     if rank == 0:
-        if args.mode == "exact" and not c3 and N > 2_000_000:
-            metric_name = "QPS at recall@10=0.95, %d x %d-d float L2 on one GPU (C4's index as one graph)" % (N, D)
-            workload = ("C4 on one GPU: %d x %d float L2, ONE device-built ANNG over all objects (not shards), "
-                        "%d queries/step, k=%d" % (N, D, NQ, K))
-        elif args.mode == "exact" and not c3:
-            metric_name = HEADLINE
-            workload = "C2: %d x %d float L2 graph search, %d queries/step/GPU, k=%d" % (N, D, NQ, K)
-        elif args.mode == "exact":
-            metric_name = "QPS at recall@10=0.95, 1M x 960-d float cosine; achieved HBM GB/s vs peak"
-            workload = "C3: %d x %d float cosine graph search, %d queries/step/GPU, k=%d" % (N, D, NQ, K)
-        elif args.mode == "qg":
-            metric_name = "QPS at recall@10=0.95, %d x %d-d NGTQG quantized graph (L2); achieved HBM GB/s" % (N, D)
-            workload = "C5 shape per GPU: %d x %d NGTQG (dsub=1, M=%d, 16 centroids), result_expansion %g, " \
-                       "%d queries/step/GPU, k=%d" % (N, D, D, args.expansion, NQ, K)
-        elif qgm:
-            metric_name = "QPS at recall@10=0.95, %d x %d-d NGTQG sharded over %d GPUs" % (N * world, D, world)
-            workload = "C5 form: %d objects per GPU shard (NGTQG dsub=1, M=%d, result_expansion %g), %d shards, " \
-                       "%d queries/step over all shards, k=%d, one packed RCCL all-gather of per-shard top-k + " \
-                       "device merge" % (N, D, args.expansion, world, NQ, K)
-        else:
-            metric_name = "QPS at recall@10=0.95, %d x %d-d float L2 sharded over %d GPUs" % (N * world, D, world)
-            workload = "C4 form: %d objects per GPU shard, %d shards, %d queries/step over all shards, k=%d, " \
-                       "one packed RCCL all-gather of per-shard top-k + device merge" % (N, world, NQ, K)
-        line = {
-            "metric": metric_name,
-            "value": qps,
-            "unit": "queries/s",
-            "n_gpus": n_ranks,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f32" if not qgm else "u4-adc/u8-lut/f32-rerank",
-            "data": "synthetic (splitmix64 U[0,1), seed 0x4E4754)",
-            "config": {"workload": workload,
-                       "recall_at_10": rec, "epsilon": chosen,
-                       "edge_size": ("all" if args.edge_size == 0 else
-                                     "%d (sc.edgeSize %d; the prf's EdgeSizeForSearch %d)" % (
-                                         es_resolved, args.edge_size, es_prop)),
-                       "graph": graph,
-                       "seeds": ("getSeedsFromTree (DVP tree leaf, seed size %d)" % args.seed_size
-                                 if args.seeds == "tree" else "getRandomSeeds (%d)" % args.seed_size),
-                       "sweep_kernel_ms_cap": SWEEP_KERNEL_MS_CAP,
-                       "distance_computations_per_query": float(c[:, 0].mean()),
-                       "expansions_per_query": float(c[:, 2].mean()),
-                       "visited_set": ("hbm-epochs, every evaluated id (accepted-only and the LDS filter are "
-                                       "off for rows over 1 KiB)" if dp * 4 > 1024 and args.visited in (-1, -2) else
-                                       {-2: "hbm-epochs+lds-filter, accepted ids only",
-                                        -1: "hbm-epochs+lds-filter"}.get(args.visited, "lds-hash")),
-                       "parallelism": ("shards x%d" % world) if shard else ("replicas x%d" % world),
-                       "distance_filter": ("1-byte filter copy (lower bound rejects neighbours outside the "
-                                           "exploration radius; exact f32 rows for the rest)" if filtered else "none"),
-                       "streams": ns_timed},
+        head["config"].update({"distance_computations_per_query": float(c[:, 0].mean()),
+                               "expansions_per_query": float(c[:, 2].mean())})
+        line = dict(head, **{
             "roofline": {"bound": "unmeasured", "achieved": achieved, "peak": PEAK_HBM_GBS, "unit": "GB/s",
                          "frac": achieved / PEAK_HBM_GBS, "traffic": traffic, "kernel": kname,
                          "kernel_ms": kernel_ms, "algorithmic_bytes_per_launch": alg_bytes,
@@ -1009,15 +1055,11 @@ def main():
             "cpu_baseline": cpu,
             "parity_sample": parity,
             "sweep": sweep,
-        }
+        })
         if stream_ms:
             line["config"]["stream_ab_ms_per_step"] = stream_ms
         if scan is not None:
             line["exact_scan"] = scan
-        if build_s is not None:
-            line["config"]["graph_build_s"] = build_s
-        if anng_check is not None:
-            line["config"]["construction_check"] = anng_check
         if ref_check is not None:
             line["config"]["reference_search_check"] = ref_check
         if latency is not None:
@@ -1143,6 +1185,28 @@ def main():
         dist.destroy_process_group()
 
 
+DUMP_MAX_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(path, ids, distances, counts, max_bytes=DUMP_MAX_BYTES):
+    """--dump-outputs: one search's results as path/{ids,distances,counts}.npy
+    (ids[nq, k] and counts[nq] as float64, exact for 32-bit ids; distances
+    [nq, k] float32).  Over max_bytes in all, the same seeded sample of the
+    queries is kept in every run and its indices written as rows.npy."""
+    os.makedirs(path, exist_ok=True)
+    nq, k = ids.shape
+    per_row = k * 12 + 16
+    rows = np.arange(nq)
+    if nq * per_row > max_bytes:
+        rows = np.sort(np.random.default_rng(BASE_SEED).choice(nq, max(1, max_bytes // per_row), replace=False))
+        np.save(os.path.join(path, "rows.npy"), rows.astype(np.float64))
+    # entries past a query's count are not part of its result: written as 0
+    valid = np.arange(k)[None, :] < counts[rows, None]
+    np.save(os.path.join(path, "ids.npy"), np.where(valid, ids[rows], 0).astype(np.float64))
+    np.save(os.path.join(path, "distances.npy"), np.where(valid, distances[rows], 0).astype(np.float32))
+    np.save(os.path.join(path, "counts.npy"), counts[rows].astype(np.float64))
+
+
 def pick_expansion(sweep, target, tie=1.03, default=3.0):
     """The result_expansion whose tuned whole-batch launch is fastest among
     those reaching the target recall (all of them if none does); launches
@@ -1257,7 +1321,7 @@ def child_line(args, name, extra, cpu_seconds, latency_queries):
     bench with its own roofline, cpu_baseline and parity sample (its JSON line
     without the sweep), or {"error": ...} if it fails."""
     cmd = [sys.executable, "-u", os.path.abspath(__file__)] + extra + [
-        "--anng-line", "off", "--c3-line", "off", "--qg-line", "off",
+        "--full", "--anng-line", "off", "--c3-line", "off", "--qg-line", "off",
         "--steps", str(max(3, min(args.steps, 5))), "--warmup", "1",
         "--cpu-seconds", str(min(args.cpu_seconds, cpu_seconds)), "--latency-queries", str(latency_queries)]
     if args.no_cpu:
@@ -1818,6 +1882,9 @@ def shard_bench(args, torch, dist, dev, rank, world, local, result_out, qgm, emi
             elapsed = float(t.item())
         qps = NQ * args.steps / elapsed
         res = [x.clone() for x in merged["r"]]
+        if args.dump_outputs and rank == 0 and emit:
+            dump_outputs(args.dump_outputs,
+                         res[0].cpu().numpy().view(np.uint32), res[1].cpu().numpy(), res[2].cpu().numpy())
         # per-launch kernel time: each shard's search alone on the main stream
         kms = []
         for s in range(S):

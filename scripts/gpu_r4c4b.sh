@@ -10,7 +10,7 @@ R="$GRAFT_REPO_ROOT"
 for pass in fetch write; do
   C=FETCH_SIZE; [ $pass = write ] && C=WRITE_SIZE
   timeout -k 10 420 rocprofv3 --pmc $C -d "$R/$O/c4_$pass" -o $pass --output-format csv -- \
-    python3 "$R/bench.py" --mode shard --shards-per-gpu 8 --eps $EPS --pmc-launches 3 --no-cpu \
+    python3 "$R/bench.py" --full --mode shard --shards-per-gpu 8 --eps $EPS --pmc-launches 3 --no-cpu \
     --latency-queries 0 > "$R/$O/c4_$pass.json" 2> "$R/$O/c4_$pass.log" || exit 1
   python3 "$R/scripts/pmc_summary.py" "$R/$O" "c4_$pass" --last 48 > /dev/null || exit 1
 done

@@ -3,7 +3,7 @@
 set -o pipefail
 cd "$GRAFT_REPO_ROOT"; O=gpurun_out/${1:-r4final}; mkdir -p $O
 bash scripts/gpu_r4.sh ${1:-r4final} || exit 1
-timeout -k 10 900 python -u bench.py > $O/bench.json 2> $O/bench.log || { tail -20 $O/bench.log; exit 1; }
+timeout -k 10 900 python -u bench.py --full > $O/bench.json 2> $O/bench.log || { tail -20 $O/bench.log; exit 1; }
 python3 scripts/jline.py $O/bench.json c2
 python3 -c "
 import json; d=json.load(open('$O/bench.json')); a=d.get('anng') or {}

@@ -8,7 +8,7 @@ cd /tmp && export TMPDIR=/tmp
 run_pass() {  # name pass counter bench-args...
   local name=$1 pass=$2 C=$3; shift 3
   timeout -k 10 ${PT:-270} rocprofv3 --pmc $C -d "$R/$O/${name}_$pass" -o $pass --output-format csv -- \
-    python3 "$R/bench.py" "$@" > "$R/$O/${name}_$pass.json" 2> "$R/$O/${name}_$pass.log" || return 1
+    python3 "$R/bench.py" --full "$@" > "$R/$O/${name}_$pass.json" 2> "$R/$O/${name}_$pass.log" || return 1
   python3 "$R/scripts/pmc_summary.py" "$R/$O" "${name}_$pass" --last 1 > /dev/null
 }
 C4="--graph anng --n 10000000 --anng-batch 8000 --eps 0.16082763671875 --pmc-launches 1 --no-cpu --latency-queries 0 --anng-line off"

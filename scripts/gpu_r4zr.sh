@@ -8,6 +8,6 @@ tail -1 $O/smoke.log
 timeout -k 10 300 python -u -m pytest -x -q --timeout 120 --timeout-method thread tests/test_gpu_parity.py \
   tests/test_gpu_build.py -m gpu > $O/pytest.log 2>&1 || { tail -30 $O/pytest.log; exit 1; }
 tail -1 $O/pytest.log
-timeout -k 10 400 python -u bench.py --steps 10 --warmup 2 --anng-line off --cpu-seconds 5 > $O/bench.json 2> $O/bench.log \
+timeout -k 10 400 python -u bench.py --full --steps 10 --warmup 2 --anng-line off --cpu-seconds 5 > $O/bench.json 2> $O/bench.log \
   || { tail -20 $O/bench.log; exit 1; }
 python3 scripts/jline.py $O/bench.json

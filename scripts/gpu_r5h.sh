@@ -9,10 +9,10 @@ timeout -k 10 600 python -u -m pytest -x -v --timeout 180 --timeout-method threa
 tail -2 $O/pytest_qg.log
 for lib in new base; do
   L=$PWD/ngt_amd/libngt_amd.so; [ $lib = base ] && L=$PWD/ngt_amd/libngt_amd_r5base.so
-  NGT_AMD_LIB=$L timeout -k 10 400 python -u bench.py --mode qg --eps 0.05625 --steps 10 --warmup 2 --no-cpu \
+  NGT_AMD_LIB=$L timeout -k 10 400 python -u bench.py --full --mode qg --eps 0.05625 --steps 10 --warmup 2 --no-cpu \
     --latency-queries 0 > $O/qg_c2_$lib.json 2> $O/qg_c2_$lib.log || { tail -20 $O/qg_c2_$lib.log; exit 1; }
   python3 scripts/jline.py $O/qg_c2_$lib.json qg_c2_$lib
-  NGT_AMD_LIB=$L timeout -k 10 500 python -u bench.py --mode qg --graph anng --n 2000000 --anng-batch 8000 \
+  NGT_AMD_LIB=$L timeout -k 10 500 python -u bench.py --full --mode qg --graph anng --n 2000000 --anng-batch 8000 \
     --eps 0.10529 --steps 5 --warmup 1 --no-cpu --latency-queries 0 > $O/qg_2m_$lib.json 2> $O/qg_2m_$lib.log \
     || { tail -20 $O/qg_2m_$lib.log; exit 1; }
   python3 scripts/jline.py $O/qg_2m_$lib.json qg_2m_$lib

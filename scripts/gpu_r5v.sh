@@ -14,7 +14,7 @@ timeout -k 10 400 python -u -m pytest -x -q --timeout 180 --timeout-method threa
 tail -1 $O/pytest.log
 run() {
   local name=$1; shift
-  env NGT_AMD_TEST_KNOBS=1 "$@" timeout -k 10 300 python -u bench.py --config c3 --eps 0.056640625 --steps 3 \
+  env NGT_AMD_TEST_KNOBS=1 "$@" timeout -k 10 300 python -u bench.py --full --config c3 --eps 0.056640625 --steps 3 \
     --warmup 1 --no-cpu --latency-queries 0 --anng-line off --c3-line off > $O/$name.json 2> $O/$name.log \
     || { tail -20 $O/$name.log; exit 1; }
   python3 scripts/jline.py $O/$name.json $name

@@ -13,7 +13,7 @@ tail -1 $O/pytest.log
 D=/tmp/anng_r5y
 for rep in a b; do
 for h in 1 2 0; do
-  NGT_AMD_TEST_KNOBS=1 NGT_AMD_LAT_HOP=$h timeout -k 10 400 python -u bench.py --graph anng --anng-dir $D --steps 1 \
+  NGT_AMD_TEST_KNOBS=1 NGT_AMD_LAT_HOP=$h timeout -k 10 400 python -u bench.py --full --graph anng --anng-dir $D --steps 1 \
     --warmup 1 --no-cpu --latency-queries 80 --capi-line off > $O/hop${h}_$rep.json 2> $O/hop${h}_$rep.log \
     || { tail -30 $O/hop${h}_$rep.log; exit 1; }
   python3 - $O/hop${h}_$rep.json hop${h}_$rep <<'PY'

@@ -11,7 +11,7 @@ D=/tmp/anng_r5za
 for rep in a b c; do
 for lib in new base; do
   L=$PWD/ngt_amd/libngt_amd.so; [ $lib = base ] && L=$PWD/ngt_amd/libngt_amd_base.so
-  NGT_AMD_LIB=$L timeout -k 10 400 python -u bench.py --graph anng --anng-dir $D --steps 1 --warmup 1 --no-cpu \
+  NGT_AMD_LIB=$L timeout -k 10 400 python -u bench.py --full --graph anng --anng-dir $D --steps 1 --warmup 1 --no-cpu \
     --latency-queries 80 --capi-line off > $O/${lib}_$rep.json 2> $O/${lib}_$rep.log || { tail -30 $O/${lib}_$rep.log; exit 1; }
   python3 - $O/${lib}_$rep.json ${lib}_$rep <<'PY'
 import json, sys

@@ -5,7 +5,7 @@ set -o pipefail
 cd "$GRAFT_REPO_ROOT"; O=gpurun_out/${1:-r5zc}; mkdir -p $O
 run() {
   local name=$1; shift
-  env "$@" timeout -k 10 300 python -u bench.py --config c3 --eps 0.056640625 --steps 3 \
+  env "$@" timeout -k 10 300 python -u bench.py --full --config c3 --eps 0.056640625 --steps 3 \
     --warmup 1 --no-cpu --latency-queries 0 --anng-line off --c3-line off > $O/$name.json 2> $O/$name.log \
     || { tail -20 $O/$name.log; exit 1; }
   python3 scripts/jline.py $O/$name.json $name

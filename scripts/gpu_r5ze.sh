@@ -11,7 +11,7 @@ L=$PWD/ngt_amd
 for rep in a b; do
   for v in w4 w3; do
     lib=$L/libngt_amd.so; [ $v = w3 ] && lib=$L/libngt_amd_c2w3.so
-    NGT_AMD_LIB=$lib timeout -k 10 300 python -u bench.py --steps 20 --warmup 5 --no-cpu --latency-queries 0 \
+    NGT_AMD_LIB=$lib timeout -k 10 300 python -u bench.py --full --steps 20 --warmup 5 --no-cpu --latency-queries 0 \
       --anng-line off --c3-line off > $O/c2_${v}_$rep.json 2> $O/c2_${v}_$rep.log || { tail -20 $O/c2_${v}_$rep.log; exit 1; }
     python3 scripts/jline.py $O/c2_${v}_$rep.json c2_${v}_$rep
   done

@@ -13,7 +13,7 @@ for rep in a b; do
   for v in base pf0 pf1; do
     lib=$L/libngt_amd.so; [ $v = base ] && lib=$L/libngt_amd_base.so
     pf=0; [ $v = pf1 ] && pf=1
-    NGT_AMD_TEST_KNOBS=1 NGT_AMD_LA_PF=$pf NGT_AMD_LIB=$lib timeout -k 10 400 python -u bench.py --graph anng \
+    NGT_AMD_TEST_KNOBS=1 NGT_AMD_LA_PF=$pf NGT_AMD_LIB=$lib timeout -k 10 400 python -u bench.py --full --graph anng \
       --anng-dir $D --steps 5 --warmup 1 --no-cpu --latency-queries 0 --capi-line off > $O/anng_${v}_$rep.json \
       2> $O/anng_${v}_$rep.log || { tail -30 $O/anng_${v}_$rep.log; exit 1; }
     python3 scripts/jline.py $O/anng_${v}_$rep.json anng_${v}_$rep

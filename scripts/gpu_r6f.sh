@@ -8,7 +8,7 @@ tail -1 $O/smoke.log
 timeout -k 10 900 python -u -m pytest -x -q --timeout 180 --timeout-method thread tests -m gpu > $O/pytest_gpu.log 2>&1 \
   || { tail -40 $O/pytest_gpu.log; exit 1; }
 tail -2 $O/pytest_gpu.log
-timeout -k 10 400 python -u bench.py --shard-line on --shard-count 2 --shard-n 250000 --anng-line off --c3-line off \
+timeout -k 10 400 python -u bench.py --full --shard-line on --shard-count 2 --shard-n 250000 --anng-line off --c3-line off \
   --qg-line off --steps 5 --warmup 1 --latency-queries 0 --cpu-seconds 5 > $O/shard.json 2> $O/shard.log \
   || { tail -30 $O/shard.log; exit 1; }
 python3 -c "

@@ -4,7 +4,7 @@
 # epsilon, streams chosen by the bench (1 at this size), parity sample
 set -o pipefail
 cd "$GRAFT_REPO_ROOT"; O=gpurun_out/${1:-r6g}; mkdir -p $O
-timeout -k 10 900 python -u bench.py --mode qg --graph anng --n 12500000 --anng-batch 8000 --eps 0.12548828125 \
+timeout -k 10 900 python -u bench.py --full --mode qg --graph anng --n 12500000 --anng-batch 8000 --eps 0.12548828125 \
   --expansion 3 --steps 5 --warmup 1 --cpu-seconds 10 --latency-queries 0 --anng-line off --streams-ab 3 \
   > $O/c5.json 2> $O/c5.log || { tail -20 $O/c5.log; exit 1; }
 python3 scripts/jline.py $O/c5.json c5

@@ -13,7 +13,7 @@ for r in 1 2; do
   for lib in nospec spec; do
     L=$PWD/ngt_amd/libngt_amd.so; [ $lib = nospec ] && L=$PWD/ngt_amd/libngt_amd_nospec.so
     C="--no-cpu"; [ $lib = spec ] && [ $r = 1 ] && C="--cpu-seconds 8"
-    NGT_AMD_LIB=$L timeout -k 10 400 python -u bench.py $A $C > $O/${lib}_$r.json 2> $O/${lib}_$r.log \
+    NGT_AMD_LIB=$L timeout -k 10 400 python -u bench.py --full $A $C > $O/${lib}_$r.json 2> $O/${lib}_$r.log \
       || { tail -20 $O/${lib}_$r.log; exit 1; }
     python3 scripts/jline.py $O/${lib}_$r.json ${lib}_$r
     grep -h "speculation\|parity" $O/${lib}_$r.log || true

@@ -12,7 +12,7 @@ A="--mode qg --graph anng --anng-dir $D --eps 0.09772 --expansion 3 --steps 10 -
 for r in 1 2; do
   for v in 0 1; do
     C="--no-cpu"; [ $v = 1 ] && [ $r = 1 ] && C="--cpu-seconds 8"
-    NGT_AMD_TEST_KNOBS=1 NGT_AMD_QG_SPEC=$v timeout -k 10 400 python -u bench.py $A $C > $O/spec${v}_$r.json \
+    NGT_AMD_TEST_KNOBS=1 NGT_AMD_QG_SPEC=$v timeout -k 10 400 python -u bench.py --full $A $C > $O/spec${v}_$r.json \
       2> $O/spec${v}_$r.log || { tail -20 $O/spec${v}_$r.log; exit 1; }
     python3 scripts/jline.py $O/spec${v}_$r.json spec${v}_$r
     grep -h "parity" $O/spec${v}_$r.log || true

@@ -11,7 +11,7 @@ D=/tmp/ngt_ab_anng_$$
 A="--graph anng --anng-dir $D --capi-line off --eps 0.1279296875 --steps 10 --warmup 2 --latency-queries 0 --no-cpu"
 for r in 1 2; do
   for ratio in 0 1.01 1.03 1.06 1.1; do
-    NGT_AMD_TEST_KNOBS=1 NGT_AMD_LA_RATIO=$ratio timeout -k 10 400 python -u bench.py $A > $O/r${ratio}_$r.json \
+    NGT_AMD_TEST_KNOBS=1 NGT_AMD_LA_RATIO=$ratio timeout -k 10 400 python -u bench.py --full $A > $O/r${ratio}_$r.json \
       2> $O/r${ratio}_$r.log || { tail -20 $O/r${ratio}_$r.log; exit 1; }
     python3 scripts/jline.py $O/r${ratio}_$r.json ratio_${ratio}_$r
     grep -h "discarded" $O/r${ratio}_$r.log || true

@@ -3,7 +3,7 @@
 # then NGTQG form) on one GPU, to time what a driver --gpus 2 run asks of a rank
 set -o pipefail
 cd "$GRAFT_REPO_ROOT"; O=gpurun_out/r6q; mkdir -p $O
-timeout -k 10 1000 python -u bench.py --gpus 1 --steps 20 --warmup 5 --shard-line on --shard-count 4 \
+timeout -k 10 1000 python -u bench.py --full --gpus 1 --steps 20 --warmup 5 --shard-line on --shard-count 4 \
   --anng-line off --qg-line off --c3-line off > $O/bench.json 2> $O/bench.log || { tail -30 $O/bench.log; exit 1; }
 python3 -c "
 import json; d=json.load(open('$O/bench.json'))

@@ -8,7 +8,7 @@ timeout -k 10 600 python -u -m pytest -x -q --timeout 300 --timeout-method threa
 tail -2 $O/pytest.log
 for r in 1 2; do for v in A B; do
   L=ngt_amd/libngt_amd_base.so; [ $v = B ] && L=ngt_amd/libngt_amd.so
-  NGT_AMD_LIB=$PWD/$L timeout -k 10 300 python3 -u bench.py --config c3 --eps 0.056640625 --steps 5 --warmup 1 --no-cpu \
+  NGT_AMD_LIB=$PWD/$L timeout -k 10 300 python3 -u bench.py --full --config c3 --eps 0.056640625 --steps 5 --warmup 1 --no-cpu \
     --latency-queries 0 --anng-line off --qg-line off --c3-line off > $O/$v$r.json 2> $O/$v$r.log || { tail -5 $O/$v$r.log; exit 1; }
   python3 -c "
 import json; d=json.load(open('$O/$v$r.json')); c=d['config']

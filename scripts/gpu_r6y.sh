@@ -7,12 +7,12 @@ timeout -k 10 600 python -u -m pytest -x -q --timeout 300 --timeout-method threa
   > $O/pytest.log 2>&1 || { tail -30 $O/pytest.log; exit 1; }
 tail -2 $O/pytest.log
 D=/tmp/ngt_y_anng_$$
-timeout -k 10 400 python3 -u bench.py --graph anng --anng-dir $D --eps 0.1279296875 --sweep-nq 10000 --steps 1 \
+timeout -k 10 400 python3 -u bench.py --full --graph anng --anng-dir $D --eps 0.1279296875 --sweep-nq 10000 --steps 1 \
   --warmup 1 --no-cpu --latency-queries 0 --capi-line off --anng-line off > $O/build.json 2> $O/build.log \
   || { tail -5 $O/build.log; exit 1; }
 for r in 1 2 3; do for v in A B; do
   L=ngt_amd/libngt_amd_base.so; [ $v = B ] && L=ngt_amd/libngt_amd.so
-  NGT_AMD_LIB=$PWD/$L timeout -k 10 300 python3 -u bench.py --mode qg --graph anng --anng-dir $D --eps 0.09772 \
+  NGT_AMD_LIB=$PWD/$L timeout -k 10 300 python3 -u bench.py --full --mode qg --graph anng --anng-dir $D --eps 0.09772 \
     --expansion 3 --sweep-nq 10000 --steps 5 --warmup 1 --no-cpu --latency-queries 0 --anng-line off --c3-line off \
     --qg-line off > $O/$v$r.json 2> $O/$v$r.log || { tail -5 $O/$v$r.log; exit 1; }
   python3 -c "

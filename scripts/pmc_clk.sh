@@ -14,6 +14,6 @@ cd /tmp && export TMPDIR=/tmp
 C=${PMC_SET:-"SQ_WAVE_CYCLES SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAIT_ANY GRBM_GUI_ACTIVE GRBM_COUNT"}
 T=${PMC_TAG:-clk}
 timeout -k 10 400 rocprofv3 --pmc $C -d "$R/$out/${name}_$T" -o $T --output-format csv -- \
-  python3 "$R/bench.py" "$@" > "$R/$out/${name}_$T.json" 2> "$R/$out/${name}_$T.log" || exit 1
+  python3 "$R/bench.py" --full "$@" > "$R/$out/${name}_$T.json" 2> "$R/$out/${name}_$T.log" || exit 1
 python3 "$R/scripts/pmc_summary.py" "$R/$out" "${name}_$T" --last ${PMC_LAST:-0} > /dev/null || exit 1
 echo "$T pass $name done"

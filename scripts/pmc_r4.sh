@@ -19,14 +19,14 @@ cd /tmp && export TMPDIR=/tmp
 TCC="TCC_HIT_sum TCC_MISS_sum TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_DRAM_sum"
 SQ="SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_INSTS_LDS SQ_WAIT_INST_LDS"
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$R/$out/${name}_trace" -o trace --output-format csv -- \
-  python3 "$R/bench.py" "$@" > "$R/$out/${name}_trace.json" 2> "$R/$out/${name}_trace.log" || exit 1
+  python3 "$R/bench.py" --full "$@" > "$R/$out/${name}_trace.json" 2> "$R/$out/${name}_trace.log" || exit 1
 find "$R/$out/${name}_trace" -name "*kernel_stats.csv" -exec cp {} "$R/$out/${name}_kernel_stats.csv" \;
 find "$R/$out/${name}_trace" -name "*kernel_trace.csv" -exec cp {} "$R/$out/${name}_kernel_trace.csv" \;
 rm -rf "$R/$out/${name}_trace"
 for pass in fetch write sq tcc; do
   case $pass in fetch) C="FETCH_SIZE";; write) C="WRITE_SIZE";; sq) C="$SQ";; tcc) C="$TCC";; esac
   timeout -k 10 400 rocprofv3 --pmc $C -d "$R/$out/${name}_$pass" -o $pass --output-format csv -- \
-    python3 "$R/bench.py" "$@" > "$R/$out/${name}_$pass.json" 2> "$R/$out/${name}_$pass.log" || exit 1
+    python3 "$R/bench.py" --full "$@" > "$R/$out/${name}_$pass.json" 2> "$R/$out/${name}_$pass.log" || exit 1
   python3 "$R/scripts/pmc_summary.py" "$R/$out" "${name}_$pass" --last ${PMC_LAST:-0} > /dev/null || exit 1
 done
 echo "pmc $name done"

@@ -82,6 +82,58 @@ def test_pick_expansion():
     assert bench.pick_expansion(sw, 0.95)["result_expansion"] == 3.0
 
 
+def test_dump_outputs_files(tmp_path):
+    """--dump-outputs: float arrays a build-to-build comparison can load, the
+    entries past each query's count zeroed, the same files from the same input."""
+    ids = np.array([[7, 3, 9], [4, 1, 2]], np.uint32)
+    dist = np.array([[0.5, 0.75, 9.0], [0.25, 1.5, 2.5]], np.float32)
+    cnt = np.array([2, 3], np.int32)
+    bench.dump_outputs(str(tmp_path / "a"), ids, dist, cnt)
+    bench.dump_outputs(str(tmp_path / "b"), ids, dist, cnt)
+    got = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in ("ids", "distances", "counts")}
+    assert got["ids"].dtype == np.float64 and got["distances"].dtype == np.float32
+    assert got["ids"].tolist() == [[7, 3, 0], [4, 1, 2]]
+    assert got["distances"].tolist() == [[0.5, 0.75, 0.0], [0.25, 1.5, 2.5]]
+    assert got["counts"].tolist() == [2, 3]
+    assert not (tmp_path / "a" / "rows.npy").exists()
+    for n in got:
+        assert (tmp_path / "a" / (n + ".npy")).read_bytes() == (tmp_path / "b" / (n + ".npy")).read_bytes()
+
+
+def test_dump_outputs_sample_is_bounded_and_fixed(tmp_path):
+    """An output over the size limit is cut to a sample of the queries that is
+    the same in every run (rows.npy names them) and fits the limit."""
+    nq, k = 1000, 10
+    ids = np.arange(nq * k, dtype=np.uint32).reshape(nq, k)
+    dist = ids.astype(np.float32)
+    cnt = np.full(nq, k, np.int32)
+    limit = 20000
+    bench.dump_outputs(str(tmp_path / "a"), ids, dist, cnt, max_bytes=limit)
+    bench.dump_outputs(str(tmp_path / "b"), ids, dist, cnt, max_bytes=limit)
+    rows = np.load(tmp_path / "a" / "rows.npy").astype(np.int64)
+    assert np.array_equal(rows, np.load(tmp_path / "b" / "rows.npy").astype(np.int64))
+    assert 0 < len(rows) < nq and np.all(np.diff(rows) > 0)
+    got = [np.load(tmp_path / "a" / (n + ".npy")) for n in ("rows", "ids", "distances", "counts")]
+    assert sum(a.nbytes for a in got) <= limit
+    assert np.array_equal(got[1], ids[rows]) and np.array_equal(got[2], dist[rows])
+
+
+def test_plain_and_full_options_parse():
+    """--full and --dump-outputs are options of the command itself (the dry
+    run takes them like any other run)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+    env.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(bench._free_port()))
+    r = subprocess.run([sys.executable, bench.__file__, "--gpus", "1", "--dry-run", "--steps", "2", "--warmup", "0",
+                        "--full", "--dump-outputs", os.devnull], env=env, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads(r.stdout.strip().splitlines()[-1])
+    assert d["steps"] == 2 and d["ms_per_step"] > 0
+
+
 def test_traffic_entries_carry_clocked_passes():
     """The four timed lines' traffic.json entries (the ones bench.py attaches
     to C2, ANNG, qg and C3) hold both clocked counter passes: the SIMD issue
