@@ -8,8 +8,20 @@
  * binding written against libngt links against libngt_amd.so unchanged for
  * the paths this build implements (open / create / append / ANNG construction
  * / search / linear search / object access / save / properties / results /
- * errors).  Graph-maintenance entry points (remove, optimizer, refine) are
- * declared for link compatibility and report an error (out of scope).
+ * errors / ONNG reconstruction).  The ngt_optimizer_* setters keep the
+ * reference's defaults and "negative or zero keeps the old value" rules
+ * (GraphOptimizer.h:63-78, :554-630); ngt_optimizer_execute runs the edge and
+ * path adjustment of GraphOptimizer::execute on the device (NGT_AMD_DEVICE) and
+ * writes grp (and prf, GraphType ONNG, when edges were adjusted), the result of
+ * `ngt reconstruct-graph -s n` byte for byte.  Search-parameter optimisation,
+ * prefetch tuning and accuracy-table generation are timing-driven and not
+ * implemented: execute fails, before it touches the output path, until
+ * ngt_optimizer_set_processing_modes(opt, false, false, false) switched them
+ * off.  That call sets the three modes its parameters name (the reference
+ * forwards them one position off, Capi.cpp:981-982).  The other graph-
+ * maintenance entry points (ngt_optimizer_adjust_search_coefficients,
+ * ngt_optimize_number_of_edges, ngt_refine_anng) are declared for link
+ * compatibility and report an error (out of scope).
  *
  * Threading: any number of threads may search one handle concurrently, as with
  * the reference (Capi.cpp:377-406).  Concurrent single-query calls with equal
@@ -21,7 +33,8 @@
  * undefined.
  *
  * Extensions (not in the reference): ngt_batch_search_index*,
- * ngt_get_last_search_counters, ngt_get_coalesce_stats, ngt_get_device_index.
+ * ngt_get_last_search_counters, ngt_get_coalesce_stats, ngt_get_device_index,
+ * ngt_optimizer_set_shortcut_reduction, ngt_optimizer_get.
  */
 #ifndef NGT_AMD_CAPI_H
 #define NGT_AMD_CAPI_H
@@ -142,6 +155,17 @@ uint32_t ngt_get_object_repository_size(NGTIndex index, NGTError error);
 NGTAnngEdgeOptimizationParameter ngt_get_anng_edge_optimization_parameter(void);
 bool ngt_optimize_number_of_edges(const char *indexPath, NGTAnngEdgeOptimizationParameter parameter,
                                   NGTError error);
+
+/* ---- extensions: the GraphOptimizer fields the reference's C API cannot
+ * reach (shortcutReduction, minNumOfEdges: the CLI's -m and -E), and a getter:
+ * values[NGT_OPTIMIZER_VALUES] = outgoing, incoming, minimum edges, queries,
+ * results, base accuracy from/to, rate accuracy from/to, gt epsilon, margin,
+ * log disabled, shortcut reduction, search-parameter optimisation, prefetch-
+ * parameter optimisation, accuracy-table generation. */
+#define NGT_OPTIMIZER_VALUES 16
+bool ngt_optimizer_set_shortcut_reduction(NGTOptimizer optimizer, bool shortcutReduction,
+                                          size_t minNumOfEdges, NGTError error);
+bool ngt_optimizer_get(NGTOptimizer optimizer, double *values, NGTError error);
 
 /* ---- extensions: distance types the reference sets only through the C++
  * NGT::Property (ngtpy.cpp:79-94 "Normalized L2"; SparseJaccard, Index.cpp:488-490) */

@@ -1,0 +1,125 @@
+/*
+ * NGT/GraphOptimizer.h -- NGT::GraphOptimizer of NGT 1.13.8
+ * (lib/NGT/GraphOptimizer.h) served by the MI355X build.
+ *
+ * Header-only, like NGT/Index.h: the public fields the reference's CLI sets
+ * (Command.cpp:740-756) are plain members, and execute() hands them to the
+ * `ngt_optimizer_*` C API of libngt_amd.so, which runs the edge and path
+ * adjustment on the GPU and writes the output index.
+ *
+ *   set, setExtension      lib/NGT/GraphOptimizer.h:545-591 (negative or zero
+ *                          keeps the old value)
+ *   setProcessingModes     :628-634
+ *   execute                :230-300
+ *
+ * The three timing-driven steps (searchParameterOptimization,
+ * prefetchParameterOptimization, accuracyTableGeneration) are not implemented
+ * by this build; they default to true as in the reference, and execute()
+ * throws while one of them is on -- switch them off as `ngt reconstruct-graph
+ * -s n` does.  adjustSearchCoefficients and optimizeNumberOfEdgesForANNG are
+ * outside this build's scope.
+ */
+#ifndef NGT_AMD_CXX_GRAPH_OPTIMIZER_H
+#define NGT_AMD_CXX_GRAPH_OPTIMIZER_H
+
+#include <string>
+#include <utility>
+
+#include "Index.h"
+
+namespace NGT {
+
+class GraphOptimizer {
+ public:
+  explicit GraphOptimizer(bool unlog = false) {
+    init();
+    logDisabled = unlog;
+  }
+  GraphOptimizer(int outgoing, int incoming, int nofqs, int nofrs, float baseAccuracyFrom, float baseAccuracyTo,
+                 float rateAccuracyFrom, float rateAccuracyTo, double gte, double m, bool unlog) {
+    init();
+    set(outgoing, incoming, nofqs, nofrs, baseAccuracyFrom, baseAccuracyTo, rateAccuracyFrom, rateAccuracyTo, gte, m);
+    logDisabled = unlog;
+  }
+
+  void init() {
+    numOfOutgoingEdges = 10;
+    numOfIncomingEdges = 120;
+    minNumOfEdges = 0;
+    numOfQueries = 100;
+    numOfResults = 20;
+    baseAccuracyRange = std::pair<float, float>(0.30f, 0.50f);
+    rateAccuracyRange = std::pair<float, float>(0.80f, 0.90f);
+    gtEpsilon = 0.1;
+    margin = 0.2;
+    logDisabled = false;
+    shortcutReduction = true;
+    searchParameterOptimization = true;
+    prefetchParameterOptimization = true;
+    accuracyTableGeneration = true;
+  }
+
+  void set(int outgoing, int incoming, int nofqs, int nofrs) {
+    if (outgoing >= 0) numOfOutgoingEdges = (size_t)outgoing;
+    if (incoming >= 0) numOfIncomingEdges = (size_t)incoming;
+    if (nofqs > 0) numOfQueries = (size_t)nofqs;
+    if (nofrs > 0) numOfResults = (size_t)nofrs;
+  }
+  void setExtension(float baseAccuracyFrom, float baseAccuracyTo, float rateAccuracyFrom, float rateAccuracyTo,
+                    double gte, double m) {
+    if (baseAccuracyFrom > 0.0) baseAccuracyRange.first = baseAccuracyFrom;
+    if (baseAccuracyTo > 0.0) baseAccuracyRange.second = baseAccuracyTo;
+    if (rateAccuracyFrom > 0.0) rateAccuracyRange.first = rateAccuracyFrom;
+    if (rateAccuracyTo > 0.0) rateAccuracyRange.second = rateAccuracyTo;
+    if (gte >= -1.0) gtEpsilon = gte;
+    if (m > 0.0) margin = m;
+  }
+  void set(int outgoing, int incoming, int nofqs, int nofrs, float baseAccuracyFrom, float baseAccuracyTo,
+           float rateAccuracyFrom, float rateAccuracyTo, double gte, double m) {
+    set(outgoing, incoming, nofqs, nofrs);
+    setExtension(baseAccuracyFrom, baseAccuracyTo, rateAccuracyFrom, rateAccuracyTo, gte, m);
+  }
+  void setProcessingModes(bool shortcut = true, bool searchParameter = true, bool prefetchParameter = true,
+                          bool accuracyTable = true) {
+    shortcutReduction = shortcut;
+    searchParameterOptimization = searchParameter;
+    prefetchParameterOptimization = prefetchParameter;
+    accuracyTableGeneration = accuracyTable;
+  }
+
+  void execute(const std::string inIndexPath, const std::string outIndexPath) {
+    detail::Err err;
+    NGTOptimizer opt = ngt_create_optimizer(logDisabled, err);
+    if (opt == NULL) err.raise("GraphOptimizer::execute");
+    // the members are size_t; values the C setters would ignore (negative) cannot occur
+    bool ok = ngt_optimizer_set_minimum(opt, (int)numOfOutgoingEdges, (int)numOfIncomingEdges, (int)numOfQueries,
+                                        (int)numOfResults, err) &&
+              ngt_optimizer_set_extension(opt, baseAccuracyRange.first, baseAccuracyRange.second,
+                                          rateAccuracyRange.first, rateAccuracyRange.second, gtEpsilon, margin, err) &&
+              ngt_optimizer_set_shortcut_reduction(opt, shortcutReduction, minNumOfEdges, err) &&
+              ngt_optimizer_set_processing_modes(opt, searchParameterOptimization, prefetchParameterOptimization,
+                                                 accuracyTableGeneration, err) &&
+              ngt_optimizer_execute(opt, inIndexPath.c_str(), outIndexPath.c_str(), err);
+    ngt_destroy_optimizer(opt);
+    if (!ok) err.raise("GraphOptimizer::execute");
+  }
+
+  size_t numOfOutgoingEdges;
+  size_t numOfIncomingEdges;
+  size_t minNumOfEdges;
+  std::pair<float, float> baseAccuracyRange;
+  std::pair<float, float> rateAccuracyRange;
+  size_t numOfQueries;
+  size_t numOfResults;
+  double gtEpsilon;
+  double margin;
+  bool logDisabled;
+  bool shortcutReduction;
+  bool searchParameterOptimization;
+  bool prefetchParameterOptimization;
+  bool accuracyTableGeneration;
+};
+
+}  // namespace NGT
+
+#endif

@@ -275,6 +275,50 @@ int ngt_amd_build_set_tree(ngt_amd_index *index, const uint32_t *leaf_parent, co
                            const void *in_pivot, const uint32_t *in_child, const float *in_border,
                            uint32_t n_internal, uint32_t root);
 
+/* ---- ONNG reconstruction -------------------------------------------------- *
+ *   ngt_amd_onng_reconstruct <- the graph stages of GraphOptimizer::execute
+ *   (lib/NGT/GraphOptimizer.h:230-296) on a host CSR graph (node v's list
+ *   ids/dists[offsets[v] .. offsets[v+1]), slot 0 the dummy, ids in [1, nrows)):
+ *   convertToANNG when input_is_anng == 0 (GraphReconstructor.h:389-423), then
+ *   reconstructGraph(graph, out, outgoing, incoming) when either is positive
+ *   (:425-561), then adjustPathsEffectively(out, min_edges) when
+ *   path_adjustment != 0 (:197-386).  Every comparison is on the stored
+ *   distances (-0 is returned as +0); the result equals the reference's edge
+ *   for edge.  Path adjustment needs lists in (distance, id) order without
+ *   repeated ids -- what the edge adjustment of a graph whose two directions
+ *   store one distance produces -- and fails with the first offending node
+ *   otherwise.  The call keeps the result for the calling thread:
+ *   ngt_amd_onng_reconstruct returns its edge count, ngt_amd_onng_get_graph
+ *   copies it out (offsets [nrows + 1]). */
+typedef struct {
+  int32_t outgoing;         /* GraphOptimizer::numOfOutgoingEdges (10)             */
+  int32_t incoming;         /* GraphOptimizer::numOfIncomingEdges (120), <= 10000  */
+  int32_t path_adjustment;  /* GraphOptimizer::shortcutReduction                   */
+  int32_t input_is_anng;    /* 0: convertToANNG first (GraphType is not ANNG)      */
+  uint64_t min_edges;       /* GraphOptimizer::minNumOfEdges (0)                   */
+} ngt_amd_onng_params;
+/* The last reconstruction of the calling thread: stage times from HIP events
+ * (conversion + edge adjustment; candidate extraction; the rank-synchronous
+ * decision with its host round trips), path candidates, peak bytes of HBM
+ * held, decision + commit launches, most decision launches one rank needed,
+ * ranks (the longest list). */
+typedef struct {
+  double edge_ms, phase_a_ms, phase_b_ms;
+  uint64_t candidates;
+  uint64_t peak_device_bytes;
+  uint32_t phase_b_launches;
+  uint32_t max_passes_per_rank;
+  uint32_t ranks;
+  uint32_t reserved;
+} ngt_amd_onng_stats;
+int ngt_amd_onng_reconstruct(int device, const uint64_t *offsets, const uint32_t *ids, const float *dists,
+                             uint64_t nrows, const ngt_amd_onng_params *params, uint64_t *out_nedges);
+int ngt_amd_onng_get_graph(uint64_t *offsets, uint32_t *ids, float *dists);
+int ngt_amd_onng_last_stats(ngt_amd_onng_stats *stats);
+/* Longest list the one-wave sort and the LDS id table take; longer lists
+ * (hubs) go through the global-memory paths. */
+uint32_t ngt_amd_onng_fast_path_capacity(void);
+
 /* ---- repository sharding (one shard per GPU) ------------ *
  * Merge of per-shard result lists gathered from every rank (RCCL all-gather
  * over xGMI): the k best (distance, global id) per query, the ordering of

@@ -24,6 +24,17 @@ class BuildParams(Structure):
                 ("reserved", c_int32)]
 
 
+class OnngParams(Structure):
+    _fields_ = [("outgoing", c_int32), ("incoming", c_int32), ("path_adjustment", c_int32),
+                ("input_is_anng", c_int32), ("min_edges", c_uint64)]
+
+
+class OnngStats(Structure):
+    _fields_ = [("edge_ms", c_double), ("phase_a_ms", c_double), ("phase_b_ms", c_double),
+                ("candidates", c_uint64), ("peak_device_bytes", c_uint64), ("phase_b_launches", c_uint32),
+                ("max_passes_per_rank", c_uint32), ("ranks", c_uint32), ("reserved", c_uint32)]
+
+
 class NGTQGQuery(Structure):
     _fields_ = [("query", POINTER(c_float)), ("size", c_size_t), ("epsilon", c_float),
                 ("result_expansion", c_float), ("radius", c_float)]
@@ -92,6 +103,10 @@ def declare(L):
         "ngt_amd_build_set_graph": (c_int, [vp, vp, vp, vp, c_uint64]),
         "ngt_amd_build_set_tree": (c_int, [vp, vp, vp, vp, vp, vp, vp, c_uint32, vp, vp, vp, vp, c_uint32,
                                            c_uint32]),
+        "ngt_amd_onng_reconstruct": (c_int, [c_int, vp, vp, vp, c_uint64, POINTER(OnngParams), u64p]),
+        "ngt_amd_onng_get_graph": (c_int, [vp, vp, vp]),
+        "ngt_amd_onng_last_stats": (c_int, [POINTER(OnngStats)]),
+        "ngt_amd_onng_fast_path_capacity": (c_uint32, []),
         "ngt_amd_merge_results_device": (c_int, [c_int, vp, vp, vp, c_uint32, c_uint32, c_uint32, vp, vp, vp, vp,
                                                  vp]),
         "ngt_amd_pack_results_device": (c_int, [c_int, vp, vp, vp, c_uint32, c_uint32, vp, vp]),
@@ -180,6 +195,17 @@ def declare(L):
         "ngt_get_error_string": (c_char_p, [vp]),
         "ngt_clear_error_string": (None, [vp]),
         "ngt_destroy_error_object": (None, [vp]),
+        "ngt_create_optimizer": (vp, [c_bool, vp]),
+        "ngt_optimizer_adjust_search_coefficients": (c_bool, [vp, c_char_p, vp]),
+        "ngt_optimizer_execute": (c_bool, [vp, c_char_p, c_char_p, vp]),
+        "ngt_optimizer_set": (c_bool, [vp, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_double,
+                                       c_double, vp]),
+        "ngt_optimizer_set_minimum": (c_bool, [vp, c_int, c_int, c_int, c_int, vp]),
+        "ngt_optimizer_set_extension": (c_bool, [vp, c_float, c_float, c_float, c_float, c_double, c_double, vp]),
+        "ngt_optimizer_set_processing_modes": (c_bool, [vp, c_bool, c_bool, c_bool, vp]),
+        "ngt_destroy_optimizer": (None, [vp]),
+        "ngt_optimizer_set_shortcut_reduction": (c_bool, [vp, c_bool, c_size_t, vp]),
+        "ngt_optimizer_get": (c_bool, [vp, POINTER(c_double), vp]),
         "ngt_get_edges": (c_bool, [vp, c_uint, vp, vp]),
         "ngt_get_object_repository_size": (c_uint32, [vp, vp]),
         "ngt_batch_search_index": (c_bool, [vp, f32p, c_uint32, c_int32, c_size_t, c_float, c_float, c_int64,

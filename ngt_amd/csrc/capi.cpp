@@ -10,7 +10,9 @@
 #include <stdlib.h>
 #include <string.h>
 #include <sys/stat.h>
+#include <unistd.h>
 
+#include <filesystem>
 #include <iostream>
 #include <memory>
 #include <mutex>
@@ -925,36 +927,223 @@ const char* ngt_get_error_string(const NGTError error) {
 void ngt_clear_error_string(NGTError error) { *static_cast<std::string*>(error) = ""; }
 void ngt_destroy_error_object(NGTError error) { delete static_cast<std::string*>(error); }
 
-NGTOptimizer ngt_create_optimizer(bool, NGTError error) {
-  set_error(error, __FUNCTION__, kNotImplemented);
-  return NULL;
+// ---- GraphOptimizer (lib/NGT/GraphOptimizer.h) -------------------------------
+// The parameters and their setters are the reference's; execute runs the graph
+// stages (edge and path adjustment) on the device (onng.cpp).  The three
+// timing-driven steps -- search-parameter optimisation, prefetch tuning,
+// accuracy-table generation -- are not reproducible and not implemented:
+// execute refuses to run while one of them is switched on.
+extern "C++" {
+namespace {
+
+struct CapiOptimizer {
+  // GraphOptimizer::init (GraphOptimizer.h:63-78)
+  size_t outgoing = 10, incoming = 120, min_edges = 0, queries = 100, results = 20;
+  float base_from = 0.30f, base_to = 0.50f, rate_from = 0.80f, rate_to = 0.90f;
+  double gt_epsilon = 0.1, margin = 0.2;
+  bool log_disabled = false;
+  bool shortcut = true, search_parameter = true, prefetch_parameter = true, accuracy_table = true;
+
+  // set(outgoing, incoming, nofqs, nofrs) (:554-567)
+  void set(int o, int i, int nofqs, int nofrs) {
+    if (o >= 0) outgoing = (size_t)o;
+    if (i >= 0) incoming = (size_t)i;
+    if (nofqs > 0) queries = (size_t)nofqs;
+    if (nofrs > 0) results = (size_t)nofrs;
+  }
+  // setExtension (:569-591)
+  void set_extension(float bf, float bt, float rf, float rt, double gte, double m) {
+    if (bf > 0.0) base_from = bf;
+    if (bt > 0.0) base_to = bt;
+    if (rf > 0.0) rate_from = rf;
+    if (rt > 0.0) rate_to = rt;
+    if (gte >= -1.0) gt_epsilon = gte;
+    if (m > 0.0) margin = m;
+  }
+};
+
+bool null_optimizer(NGTError error, const char* func) {
+  // the reference streams the NULL pointer (Capi.cpp:872-876)
+  return param_error(error, func, "optimizer = 0");
 }
-bool ngt_optimizer_adjust_search_coefficients(NGTOptimizer, const char*, NGTError error) {
+
+std::string write_grp(const std::string& path, const HostIndex& h, const std::vector<uint64_t>& off,
+                      const std::vector<uint32_t>& ids, const std::vector<float>& dists) {
+  // GraphRepository::serialize (Graph.h:151-154), as index_io.cpp's save_index
+  FILE* f = fopen(path.c_str(), "wb");
+  if (!f) return "cannot write " + path;
+  std::vector<char> buf;
+  auto put = [&buf](const void* p, size_t n) { buf.insert(buf.end(), (const char*)p, (const char*)p + n); };
+  const uint64_t n = h.nrows;
+  put(&n, 8);
+  for (uint64_t i = 0; i < n; i++) {
+    // a slot holds a node when the input graph had one (an object, or edges)
+    if (i == 0 || (!h.valid[i] && h.edge_off[i] == h.edge_off[i + 1])) {
+      put("-", 1);
+      continue;
+    }
+    put("+", 1);
+    const uint32_t cnt = (uint32_t)(off[i + 1] - off[i]);
+    put(&cnt, 4);
+    for (uint64_t j = off[i]; j < off[i + 1]; j++) {
+      put(&ids[j], 4);
+      put(&dists[j], 4);
+    }
+  }
+  const uint32_t ps = (uint32_t)h.prevsize.size();
+  put(&ps, 4);
+  if (ps) put(h.prevsize.data(), (size_t)ps * 2);
+  const bool ok = fwrite(buf.data(), 1, buf.size(), f) == buf.size();
+  return (fclose(f) == 0 && ok) ? "" : "cannot write " + path;
+}
+
+// GraphOptimizer::execute (GraphOptimizer.h:230-300)
+std::string optimizer_execute(const CapiOptimizer& o, const std::string& in_path, const std::string& out_path) {
+  if (o.search_parameter || o.prefetch_parameter || o.accuracy_table)
+    return "Optimizer::execute: search-parameter optimization, prefetch-parameter optimization and accuracy-table "
+           "generation are timing-driven and not implemented in the MI355X build; "
+           "ngt_optimizer_set_processing_modes(opt, false, false, false) is required.";
+  if (access(out_path.c_str(), 0) == 0) return "Optimizer::execute: The specified index exists. " + out_path;
+  if (o.incoming > 10000) return "Optimizer::execute: something wrong. Edge size=" + std::to_string(o.incoming);
+  std::error_code ec;
+  std::filesystem::copy(in_path, out_path, std::filesystem::copy_options::recursive, ec);
+  if (ec) {
+    std::filesystem::remove_all(out_path, ec);
+    return "Optimizer::execute: Cannot create the specified index. " + out_path;
+  }
+  std::string e;
+  {
+    HostIndex h;
+    e = ngt_amd::load_index(out_path, h);
+    const bool edge = o.outgoing > 0 || o.incoming > 0;
+    if (e.empty() && (edge || o.shortcut)) {
+      ngt_amd_onng_params p{};
+      p.outgoing = (int32_t)std::min<size_t>(o.outgoing, INT32_MAX);
+      p.incoming = (int32_t)o.incoming;
+      p.path_adjustment = o.shortcut ? 1 : 0;
+      p.input_is_anng = h.prop.graph_type == 1 ? 1 : 0;
+      p.min_edges = o.min_edges;
+      int dev = 0;
+      if (const char* env = getenv("NGT_AMD_DEVICE")) dev = atoi(env);
+      uint64_t ne = 0;
+      if (ngt_amd_onng_reconstruct(dev, h.edge_off.data(), h.edges.data(), h.edge_dists.data(), h.nrows, &p, &ne)) {
+        e = amd_err();
+      } else {
+        std::vector<uint64_t> off(h.nrows + 1);
+        std::vector<uint32_t> ids(ne);
+        std::vector<float> dists(ne);
+        if (ngt_amd_onng_get_graph(off.data(), ids.data(), dists.data())) e = amd_err();
+        if (e.empty()) e = write_grp(out_path + "/grp", h, off, ids, dists);
+        if (e.empty() && edge) {
+          h.prop.graph_type = 4;  // GraphTypeONNG
+          e = ngt_amd::write_prf(out_path + "/prf", h.prop);
+        }
+      }
+    }
+  }
+  if (!e.empty()) std::filesystem::remove_all(out_path, ec);  // nothing half-made stays behind
+  return e;
+}
+
+}  // namespace
+}  // extern "C++"
+
+NGTOptimizer ngt_create_optimizer(bool logDisabled, NGTError error) {
+  try {
+    CapiOptimizer* o = new CapiOptimizer();
+    o->log_disabled = logDisabled;
+    return static_cast<NGTOptimizer>(o);
+  } catch (std::exception& err) {
+    set_error(error, __FUNCTION__, err.what());
+    return NULL;
+  }
+}
+bool ngt_optimizer_adjust_search_coefficients(NGTOptimizer optimizer, const char*, NGTError error) {
+  if (optimizer == NULL) return !null_optimizer(error, __FUNCTION__);
   set_error(error, __FUNCTION__, kNotImplemented);
   return false;
 }
-bool ngt_optimizer_execute(NGTOptimizer, const char*, const char*, NGTError error) {
-  set_error(error, __FUNCTION__, kNotImplemented);
-  return false;
+bool ngt_optimizer_execute(NGTOptimizer optimizer, const char* inIndex, const char* outIndex, NGTError error) {
+  if (optimizer == NULL) return !null_optimizer(error, __FUNCTION__);
+  if (inIndex == NULL || outIndex == NULL) {
+    param_error(error, __FUNCTION__, "index path = 0");
+    return false;
+  }
+  try {
+    std::string e = optimizer_execute(*static_cast<CapiOptimizer*>(optimizer), inIndex, outIndex);
+    if (!e.empty()) {
+      set_error(error, __FUNCTION__, e);
+      return false;
+    }
+  } catch (std::exception& err) {
+    set_error(error, __FUNCTION__, err.what());
+    return false;
+  }
+  return true;
 }
-bool ngt_optimizer_set(NGTOptimizer, int, int, int, float, float, float, float, double, double,
+// obsolete in the reference "because of a lack of a parameter" (GraphOptimizer.h:593-626)
+bool ngt_optimizer_set(NGTOptimizer optimizer, int outgoing, int incoming, int nofqs, float baseAccuracyFrom,
+                       float baseAccuracyTo, float rateAccuracyFrom, float rateAccuracyTo, double gte, double m,
                        NGTError error) {
-  set_error(error, __FUNCTION__, kNotImplemented);
-  return false;
+  if (optimizer == NULL) return !null_optimizer(error, __FUNCTION__);
+  CapiOptimizer* o = static_cast<CapiOptimizer*>(optimizer);
+  o->set(outgoing, incoming, nofqs, 0);
+  o->set_extension(baseAccuracyFrom, baseAccuracyTo, rateAccuracyFrom, rateAccuracyTo, gte, m);
+  return true;
 }
-bool ngt_optimizer_set_minimum(NGTOptimizer, int, int, int, int, NGTError error) {
-  set_error(error, __FUNCTION__, kNotImplemented);
-  return false;
+bool ngt_optimizer_set_minimum(NGTOptimizer optimizer, int outgoing, int incoming, int nofqs, int nofrs,
+                               NGTError error) {
+  if (optimizer == NULL) return !null_optimizer(error, __FUNCTION__);
+  static_cast<CapiOptimizer*>(optimizer)->set(outgoing, incoming, nofqs, nofrs);
+  return true;
 }
-bool ngt_optimizer_set_extension(NGTOptimizer, float, float, float, float, double, double, NGTError error) {
-  set_error(error, __FUNCTION__, kNotImplemented);
-  return false;
+bool ngt_optimizer_set_extension(NGTOptimizer optimizer, float baseAccuracyFrom, float baseAccuracyTo,
+                                 float rateAccuracyFrom, float rateAccuracyTo, double gte, double m,
+                                 NGTError error) {
+  if (optimizer == NULL) return !null_optimizer(error, __FUNCTION__);
+  static_cast<CapiOptimizer*>(optimizer)->set_extension(baseAccuracyFrom, baseAccuracyTo, rateAccuracyFrom,
+                                                        rateAccuracyTo, gte, m);
+  return true;
 }
-bool ngt_optimizer_set_processing_modes(NGTOptimizer, bool, bool, bool, NGTError error) {
-  set_error(error, __FUNCTION__, kNotImplemented);
-  return false;
+// The three modes as the header names them.  (The reference forwards them to a
+// four-argument setProcessingModes whose first parameter is the shortcut
+// reduction, Capi.cpp:981-982, so there they land one position off.)
+bool ngt_optimizer_set_processing_modes(NGTOptimizer optimizer, bool searchParameter, bool prefetchParameter,
+                                        bool accuracyTable, NGTError error) {
+  if (optimizer == NULL) return !null_optimizer(error, __FUNCTION__);
+  CapiOptimizer* o = static_cast<CapiOptimizer*>(optimizer);
+  o->search_parameter = searchParameter;
+  o->prefetch_parameter = prefetchParameter;
+  o->accuracy_table = accuracyTable;
+  return true;
 }
-void ngt_destroy_optimizer(NGTOptimizer) {}
+bool ngt_optimizer_set_shortcut_reduction(NGTOptimizer optimizer, bool shortcutReduction, size_t minNumOfEdges,
+                                          NGTError error) {
+  if (optimizer == NULL) return !null_optimizer(error, __FUNCTION__);
+  CapiOptimizer* o = static_cast<CapiOptimizer*>(optimizer);
+  o->shortcut = shortcutReduction;
+  o->min_edges = minNumOfEdges;
+  return true;
+}
+bool ngt_optimizer_get(NGTOptimizer optimizer, double* values, NGTError error) {
+  if (optimizer == NULL) return !null_optimizer(error, __FUNCTION__);
+  if (values == NULL) {
+    param_error(error, __FUNCTION__, "values = 0");
+    return false;
+  }
+  const CapiOptimizer& o = *static_cast<CapiOptimizer*>(optimizer);
+  const double v[NGT_OPTIMIZER_VALUES] = {(double)o.outgoing, (double)o.incoming, (double)o.min_edges,
+                                          (double)o.queries, (double)o.results, o.base_from, o.base_to,
+                                          o.rate_from, o.rate_to, o.gt_epsilon, o.margin, (double)o.log_disabled,
+                                          (double)o.shortcut, (double)o.search_parameter,
+                                          (double)o.prefetch_parameter, (double)o.accuracy_table};
+  memcpy(values, v, sizeof v);
+  return true;
+}
+void ngt_destroy_optimizer(NGTOptimizer optimizer) {
+  if (optimizer == NULL) return;
+  delete static_cast<CapiOptimizer*>(optimizer);
+}
 bool ngt_refine_anng(NGTIndex, float, float, int, int, size_t, NGTError error) {
   set_error(error, __FUNCTION__, kNotImplemented);
   return false;

@@ -16,6 +16,7 @@ from . import NativeError
 from . import base
 
 FLT_MAX = 3.4028234663852886e38
+DBL_MAX = 1.7976931348623157e308
 INT_MIN = -(2 ** 31)
 
 
@@ -189,3 +190,69 @@ class Index(object):
 
     def close(self):
         self._ix.close()
+
+
+class Optimizer(object):
+    """ngtpy.Optimizer (ngtpy.cpp:566-600): NGT::GraphOptimizer with the
+    reference's argument names and defaults (negative values keep the
+    optimizer's own defaults, GraphOptimizer.h:63-78, :545-591).  ``execute``
+    runs edge and path adjustment on the MI355X; the three tuning steps have to
+    be switched off with ``set_processing_modes`` first."""
+
+    def __init__(self, num_of_outgoings=-1, num_of_incomings=-1, num_of_queries=-1, num_of_objects=-1,
+                 low_accuracy_from=-1.0, low_accuracy_to=-1.0, high_accuracy_from=-1.0, high_accuracy_to=-1.0,
+                 gt_epsilon=-DBL_MAX, margin=-1.0, log_disabled=False):
+        from . import lib
+        self._L = lib()
+        self._err = self._L.ngt_create_error_object()
+        self._opt = self._L.ngt_create_optimizer(bool(log_disabled), self._err)
+        if not self._opt:
+            raise NativeError(base._err_string(self._L, self._err))
+        self._min_edges = 0
+        self.set(num_of_outgoings, num_of_incomings, num_of_queries, num_of_objects, low_accuracy_from,
+                 low_accuracy_to, high_accuracy_from, high_accuracy_to, gt_epsilon, margin)
+
+    def __del__(self):
+        if getattr(self, "_opt", None):
+            self._L.ngt_destroy_optimizer(self._opt)
+            self._opt = None
+        if getattr(self, "_err", None):
+            self._L.ngt_destroy_error_object(self._err)
+            self._err = None
+
+    def _check(self, ok):
+        if not ok:
+            raise NativeError(base._err_string(self._L, self._err))
+
+    def set(self, num_of_outgoings=-1, num_of_incomings=-1, num_of_queries=-1, num_of_objects=-1,
+            low_accuracy_from=-1.0, low_accuracy_to=-1.0, high_accuracy_from=-1.0, high_accuracy_to=-1.0,
+            gt_epsilon=-DBL_MAX, margin=-1.0):
+        """GraphOptimizer::set(outgoing, incoming, nofqs, nofrs, ...) (GraphOptimizer.h:545-552)."""
+        L = self._L
+        self._check(L.ngt_optimizer_set_minimum(self._opt, int(num_of_outgoings), int(num_of_incomings),
+                                                int(num_of_queries), int(num_of_objects), self._err))
+        self._check(L.ngt_optimizer_set_extension(self._opt, low_accuracy_from, low_accuracy_to, high_accuracy_from,
+                                                  high_accuracy_to, gt_epsilon, margin, self._err))
+
+    def set_processing_modes(self, shortcut_reduction=True, search_parameter_optimization=True,
+                             prefetch_parameter_optimization=True, accuracy_table_generation=True):
+        L = self._L
+        self._check(L.ngt_optimizer_set_shortcut_reduction(self._opt, bool(shortcut_reduction), self._min_edges,
+                                                           self._err))
+        self._check(L.ngt_optimizer_set_processing_modes(self._opt, bool(search_parameter_optimization),
+                                                         bool(prefetch_parameter_optimization),
+                                                         bool(accuracy_table_generation), self._err))
+
+    def get(self):
+        """The optimizer's parameters by name (not in the reference)."""
+        import ctypes
+        v = (ctypes.c_double * 16)()
+        self._check(self._L.ngt_optimizer_get(self._opt, v, self._err))
+        names = ("num_of_outgoings", "num_of_incomings", "min_num_of_edges", "num_of_queries", "num_of_objects",
+                 "low_accuracy_from", "low_accuracy_to", "high_accuracy_from", "high_accuracy_to", "gt_epsilon",
+                 "margin", "log_disabled", "shortcut_reduction", "search_parameter_optimization",
+                 "prefetch_parameter_optimization", "accuracy_table_generation")
+        return dict(zip(names, list(v)))
+
+    def execute(self, in_path, out_path):
+        self._check(self._L.ngt_optimizer_execute(self._opt, os.fsencode(in_path), os.fsencode(out_path), self._err))
