@@ -18,10 +18,18 @@
  * implemented: execute fails, before it touches the output path, until
  * ngt_optimizer_set_processing_modes(opt, false, false, false) switched them
  * off.  That call sets the three modes its parameters name (the reference
- * forwards them one position off, Capi.cpp:981-982).  The other graph-
+ * forwards them one position off, Capi.cpp:981-982).  ngt_refine_anng is
+ * GraphReconstructor::refineANNG (GraphReconstructor.h:803-924) on the device,
+ * in place on the handle under the lock appends take: one search per stored
+ * object in batches, outgoing and incoming edges, the final prune; a save then
+ * writes the grp of `ngt refine-anng` byte for byte (the reference run with one
+ * thread: with several, its seed thinning shares rand() between threads).  Two
+ * deviations: on an error the handle's graph is left as it was (the reference
+ * keeps the batches it finished), and batchSize == 0 is an error (the reference
+ * never leaves its loop).  It needs a GraphAndTree index.  The other graph-
  * maintenance entry points (ngt_optimizer_adjust_search_coefficients,
- * ngt_optimize_number_of_edges, ngt_refine_anng) are declared for link
- * compatibility and report an error (out of scope).
+ * ngt_optimize_number_of_edges) are declared for link compatibility and report
+ * an error (out of scope).
  *
  * Threading: any number of threads may search one handle concurrently, as with
  * the reference (Capi.cpp:377-406).  Concurrent single-query calls with equal

@@ -21,9 +21,10 @@
  *   NGT::ObjectSpace     lib/NGT/ObjectSpace.h:146-292 (enums, getObject)
  *
  * Errors surface as NGT::Exception carrying the C API's message.  Entry points
- * of graph maintenance (remove, refine) and graph-only construction throw:
- * they are outside this build's scope.  The ONNG reconstruction is
- * NGT::GraphOptimizer (NGT/GraphOptimizer.h).
+ * of graph maintenance (remove) and graph-only construction throw: they are
+ * outside this build's scope.  The ONNG reconstruction is NGT::GraphOptimizer
+ * (NGT/GraphOptimizer.h), refine-anng is NGT::GraphReconstructor::refineANNG
+ * (NGT/GraphReconstructor.h).
  */
 #ifndef NGT_AMD_CXX_INDEX_H
 #define NGT_AMD_CXX_INDEX_H

@@ -319,6 +319,61 @@ int ngt_amd_onng_last_stats(ngt_amd_onng_stats *stats);
  * (hubs) go through the global-memory paths. */
 uint32_t ngt_amd_onng_fast_path_capacity(void);
 
+/* ---- refine-anng ---------------------------------------------------------- *
+ *   ngt_amd_refine_anng <- GraphReconstructor::refineANNG
+ *   (lib/NGT/GraphReconstructor.h:803-924): per batch of batch_size ids, one
+ *   search per stored object (the object is the query; size = -num_edges when
+ *   num_edges < 0, else max(num_edges, edge_size_for_creation); tree seeds),
+ *   then every batch node's list takes its results (without itself, sorted by
+ *   (distance, id), adjacent repeats of an id dropped) and, when num_edges == 0,
+ *   every result's node takes the reverse edge (addEdge, Graph.h:845-873); after
+ *   the last batch num_edges > 0 cuts every list to num_edges.  The graph of
+ *   one batch is the input of the next.  The result equals the reference's edge
+ *   for edge (-0 is returned as +0).
+ *   The index has rows and a tree; `offsets/ids/dists` is its graph with
+ *   distances (host CSR of nrows = the index's rows, node v's list
+ *   ids/dists[offsets[v] .. offsets[v+1]), slot 0 the dummy, every list in
+ *   (distance, id) order).  Queries, results
+ *   and the graph stay in HBM from batch to batch.  On success the index
+ *   searches the refined graph; on failure it searches the input graph again.
+ *   ngt_amd_refine_merge applies the two list steps to a given graph and one
+ *   block of results (query q is node first_id + q, its results
+ *   res_ids/res_dists[q * stride .. + res_counts[q]); a block that overhangs
+ *   the rows is cut); ngt_amd_refine_prune applies the final cut.  Each call
+ *   keeps its result for the calling thread, as ngt_amd_onng_reconstruct does. */
+typedef struct {
+  float epsilon;                 /* SearchContainer::setEpsilon                          */
+  int32_t num_edges;             /* noOfEdges                                            */
+  int64_t explore_edge_size;     /* SearchContainer::edgeSize; -1 = EdgeSizeForSearch    */
+  uint64_t batch_size;           /* > 0                                                  */
+  int32_t edge_size_for_creation;/* the prf's EdgeSizeForCreation                        */
+  int32_t reserved;
+} ngt_amd_refine_params;
+/* The last refinement of the calling thread: wall time of the searches, of the
+ * list steps and of the search-adjacency refresh (the stream synchronised at
+ * each boundary) and of the whole call; batches, searches, incoming candidates
+ * extracted, edges before and after, kernel launches of the list steps (they
+ * depend on the graph alone), the longest list. */
+typedef struct {
+  double search_ms, merge_ms, refresh_ms, total_ms;
+  uint64_t batches, searched, candidates, edges_in, edges_out;
+  uint32_t launches;
+  uint32_t longest_list;
+} ngt_amd_refine_stats;
+int ngt_amd_refine_anng(ngt_amd_index *index, const uint64_t *offsets, const uint32_t *ids, const float *dists,
+                        uint64_t nrows, const ngt_amd_refine_params *params, uint64_t *out_nedges);
+int ngt_amd_refine_merge(int device, const uint64_t *offsets, const uint32_t *ids, const float *dists,
+                         uint64_t nrows, uint32_t first_id, uint32_t count, uint32_t stride,
+                         const uint32_t *res_ids, const float *res_dists, const uint32_t *res_counts,
+                         int incoming, uint64_t *out_nedges);
+int ngt_amd_refine_prune(int device, const uint64_t *offsets, const uint32_t *ids, const float *dists,
+                         uint64_t nrows, uint32_t num_edges, uint64_t *out_nedges);
+int ngt_amd_refine_get_graph(uint64_t *offsets, uint32_t *ids, float *dists);
+int ngt_amd_refine_last_stats(ngt_amd_refine_stats *stats);
+/* Longest list the one-wave sort takes; longer lists (hubs) are sorted in
+ * global memory.  The other list kernels have no such limit. */
+uint32_t ngt_amd_refine_fast_path_capacity(void);
+
 /* ---- repository sharding (one shard per GPU) ------------ *
  * Merge of per-shard result lists gathered from every rank (RCCL all-gather
  * over xGMI): the k best (distance, global id) per query, the ordering of

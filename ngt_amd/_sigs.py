@@ -29,6 +29,17 @@ class OnngParams(Structure):
                 ("input_is_anng", c_int32), ("min_edges", c_uint64)]
 
 
+class RefineParams(Structure):
+    _fields_ = [("epsilon", c_float), ("num_edges", c_int32), ("explore_edge_size", c_int64),
+                ("batch_size", c_uint64), ("edge_size_for_creation", c_int32), ("reserved", c_int32)]
+
+
+class RefineStats(Structure):
+    _fields_ = [("search_ms", c_double), ("merge_ms", c_double), ("refresh_ms", c_double), ("total_ms", c_double),
+                ("batches", c_uint64), ("searched", c_uint64), ("candidates", c_uint64), ("edges_in", c_uint64),
+                ("edges_out", c_uint64), ("launches", c_uint32), ("longest_list", c_uint32)]
+
+
 class OnngStats(Structure):
     _fields_ = [("edge_ms", c_double), ("phase_a_ms", c_double), ("phase_b_ms", c_double),
                 ("candidates", c_uint64), ("peak_device_bytes", c_uint64), ("phase_b_launches", c_uint32),
@@ -107,6 +118,13 @@ def declare(L):
         "ngt_amd_onng_get_graph": (c_int, [vp, vp, vp]),
         "ngt_amd_onng_last_stats": (c_int, [POINTER(OnngStats)]),
         "ngt_amd_onng_fast_path_capacity": (c_uint32, []),
+        "ngt_amd_refine_anng": (c_int, [vp, vp, vp, vp, c_uint64, POINTER(RefineParams), u64p]),
+        "ngt_amd_refine_merge": (c_int, [c_int, vp, vp, vp, c_uint64, c_uint32, c_uint32, c_uint32, vp, vp, vp,
+                                         c_int, u64p]),
+        "ngt_amd_refine_prune": (c_int, [c_int, vp, vp, vp, c_uint64, c_uint32, u64p]),
+        "ngt_amd_refine_get_graph": (c_int, [vp, vp, vp]),
+        "ngt_amd_refine_last_stats": (c_int, [POINTER(RefineStats)]),
+        "ngt_amd_refine_fast_path_capacity": (c_uint32, []),
         "ngt_amd_merge_results_device": (c_int, [c_int, vp, vp, vp, c_uint32, c_uint32, c_uint32, vp, vp, vp, vp,
                                                  vp]),
         "ngt_amd_pack_results_device": (c_int, [c_int, vp, vp, vp, c_uint32, c_uint32, vp, vp]),
@@ -206,6 +224,7 @@ def declare(L):
         "ngt_destroy_optimizer": (None, [vp]),
         "ngt_optimizer_set_shortcut_reduction": (c_bool, [vp, c_bool, c_size_t, vp]),
         "ngt_optimizer_get": (c_bool, [vp, POINTER(c_double), vp]),
+        "ngt_refine_anng": (c_bool, [vp, c_float, c_float, c_int, c_int, c_size_t, vp]),
         "ngt_get_edges": (c_bool, [vp, c_uint, vp, vp]),
         "ngt_get_object_repository_size": (c_uint32, [vp, vp]),
         "ngt_batch_search_index": (c_bool, [vp, f32p, c_uint32, c_int32, c_size_t, c_float, c_float, c_int64,

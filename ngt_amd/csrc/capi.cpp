@@ -1144,9 +1144,116 @@ void ngt_destroy_optimizer(NGTOptimizer optimizer) {
   if (optimizer == NULL) return;
   delete static_cast<CapiOptimizer*>(optimizer);
 }
-bool ngt_refine_anng(NGTIndex, float, float, int, int, size_t, NGTError error) {
-  set_error(error, __FUNCTION__, kNotImplemented);
-  return false;
+// ---- refine-anng (GraphReconstructor::refineANNG, GraphReconstructor.h:803-924)
+extern "C++" {
+namespace {
+
+// Index::AccuracyTable::set (Index.h:299-315) of the prf's AccuracyTable, then
+// getEpsilon (:317-346) in the reference's mixed float/double arithmetic.
+std::string epsilon_from_accuracy(const HostProperty& prop, double accuracy, float& epsilon) {
+  std::vector<std::pair<float, double>> table;
+  auto it = prop.kv.find("AccuracyTable");
+  const std::string text = it == prop.kv.end() ? "" : it->second;
+  auto tokenize = [](const std::string& s, char sep) {
+    std::vector<std::string> out;
+    size_t b = 0;
+    while (b <= s.size()) {
+      size_t e = s.find(sep, b);
+      if (e == std::string::npos) e = s.size();
+      if (e > b) out.push_back(s.substr(b, e - b));
+      b = e + 1;
+    }
+    return out;
+  };
+  const std::vector<std::string> tokens = tokenize(text, ',');
+  if (tokens.size() >= 2) {
+    for (const std::string& t : tokens) {
+      const std::vector<std::string> ts = tokenize(t, ':');
+      if (ts.size() != 2) return "AccuracyTable: Invalid accuracy table string " + t + ":" + text;
+      table.push_back({(float)strtod(ts[0].c_str(), nullptr), strtod(ts[1].c_str(), nullptr)});
+    }
+  }
+  if (table.size() <= 2)
+    return "AccuracyTable: The accuracy table is not set yet. The table size=" + std::to_string(table.size());
+  if (accuracy > 1.0) accuracy = 1.0;
+  size_t i = 0;
+  while (i < table.size() && table[i].second < accuracy) i++;
+  if (i == table.size()) i -= 2;
+  else if (i != 0) i--;
+  const std::pair<float, double> lower = table[i], upper = table[i + 1];
+  float e = (float)((double)lower.first +
+                    (double)(upper.first - lower.first) * (accuracy - lower.second) / (upper.second - lower.second));
+  if (e < -0.9) e = (float)-0.9;
+  epsilon = e;
+  return "";
+}
+
+// In place on the handle, under the write lock appends take.  Deviations from
+// the reference: any error leaves the handle's graph as it was (the reference
+// keeps the batches it finished), and a batch size of 0 is an error (the
+// reference never leaves its loop).
+std::string refine_anng(CapiIndex* ix, float epsilon, float accuracy, int num_edges, int explore, size_t batch_size) {
+  const std::string who = "GraphReconstructor::refineANNG: ";
+  std::unique_lock<std::shared_mutex> wl(ix->rw);
+  HostIndex& h = ix->host;
+  if (batch_size == 0) return who + "the batch size is 0";
+  if (h.nrows < 2) return "";  // no object: the reference's loop does not run
+  if (h.edge_off.size() != h.nrows + 1 || h.edge_dists.size() != h.edges.size())
+    return who + "graph arrays inconsistent with the repository";
+  if (!use_tree(ix)) return who + "the MI355X build refines GraphAndTree indexes only (the searches take tree seeds)";
+  if (accuracy > 0.0f) {
+    std::string e = epsilon_from_accuracy(h.prop, (double)accuracy, epsilon);
+    if (!e.empty()) return who + e;
+  }
+  if (explore != INT_MIN && explore < -2)  // getEdgeSize, before any device work
+    return who + "NGT::getEdgeSize: Invalid edge size parameters " + std::to_string(explore) + ":" +
+           std::to_string(h.prop.edge_size_for_search);
+  std::string e = rebuild_device(ix);
+  if (!e.empty()) return who + e;
+  ngt_amd_refine_params p{};
+  p.epsilon = epsilon;
+  p.num_edges = num_edges;
+  p.explore_edge_size = explore == INT_MIN ? -1 : explore;
+  p.batch_size = batch_size;
+  p.edge_size_for_creation = h.prop.edge_size_for_creation;
+  uint64_t ne = 0;
+  if (ngt_amd_refine_anng(ix->dev, h.edge_off.data(), h.edges.data(), h.edge_dists.data(), h.nrows, &p, &ne)) {
+    ix->device_stale = true;  // the next search rebuilds the device copy from the untouched mirror
+    return who + amd_err();
+  }
+  std::vector<uint64_t> off(h.nrows + 1);
+  std::vector<uint32_t> ids(ne);
+  std::vector<float> dists(ne);
+  if (ngt_amd_refine_get_graph(off.data(), ids.data(), dists.data())) {
+    ix->device_stale = true;
+    return who + amd_err();
+  }
+  h.edge_off.swap(off);
+  h.edges.swap(ids);
+  h.edge_dists.swap(dists);
+  return "";  // the device copy already searches the refined graph
+}
+
+}  // namespace
+}  // extern "C++"
+
+bool ngt_refine_anng(NGTIndex index, float epsilon, float accuracy, int noOfEdges, int exploreEdgeSize,
+                     size_t batchSize, NGTError error) {
+  if (index == NULL) {
+    param_error(error, __FUNCTION__, "index = 0");
+    return false;
+  }
+  try {
+    std::string e = refine_anng(static_cast<CapiIndex*>(index), epsilon, accuracy, noOfEdges, exploreEdgeSize, batchSize);
+    if (!e.empty()) {
+      set_error(error, __FUNCTION__, e);
+      return false;
+    }
+  } catch (std::exception& err) {
+    set_error(error, __FUNCTION__, err.what());
+    return false;
+  }
+  return true;
 }
 
 bool ngt_get_edges(NGTIndex index, ObjectID id, NGTObjectDistances edges, NGTError error) {

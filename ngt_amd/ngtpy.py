@@ -183,6 +183,20 @@ class Index(object):
         L = self._ix._L
         self._ix._check(L.ngt_remove_index(self._ix.index, self._id_in(object_id), self._ix.err), self._ix.err)
 
+    def refine_anng(self, epsilon=0.1, expected_accuracy=0.0, num_of_edges=0, num_of_explored_edges=INT_MIN,
+                    batch_size=10000):
+        """ngtpy.cpp:548-553 -> GraphReconstructor::refineANNG: one search per
+        stored object on the GPU in batches, the results merged into the graph
+        in place (outgoing edges; incoming edges when num_of_edges is 0; every
+        list cut to num_of_edges when it is positive).  ``save`` then writes
+        what ``ngt refine-anng`` writes.  On an error the graph is left as it
+        was; a batch_size of 0 is an error."""
+        L = self._ix._L
+        self._ix._check(L.ngt_refine_anng(self._ix.index, float(epsilon), float(expected_accuracy),
+                                          int(num_of_edges), int(num_of_explored_edges), int(batch_size),
+                                          self._ix.err), self._ix.err)
+        self._table = None
+
     def save(self):
         if self.read_only:
             raise NativeError("ngtpy::save: the index is read only")
