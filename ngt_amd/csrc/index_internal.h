@@ -13,6 +13,7 @@
 
 #include "../../include/ngt_amd.h"
 #include "ngt_kernels.h"
+#include "search_plan.h"
 
 namespace ngt_amd {
 
@@ -118,7 +119,7 @@ struct SearchCtx {
   DevBuf<uint32_t> ivf_cid, ivf_cn;  // NGTQ: global-codebook search results [nq][cbs], [nq]
   DevBuf<float> ivf_cd;
   DevBuf<int> err;               // device error flag of the launches on this stream
-  // launch schedule ("probe and resume", ngt_amd_api.cpp run_search): the
+  // launch schedule ("probe and resume", ngt_amd_api.cpp launch_planned): the
   // paused queries' states, flags, predictions and the resume order; the
   // mean expansions per query of earlier launches of the same configuration
   // (a pinned copy of the device sums, read once the launch has finished)
@@ -318,6 +319,11 @@ float coef_of(float epsilon);
 // caller holds ix->mu), and the edges a search of resolved edge size es reads
 int build_padded_adjacency(ngt_amd_index* ix, uint64_t need);
 uint64_t adjacency_need(const ngt_amd_index* ix, uint64_t es);
+// the index's fields of SearchArgs for a search of resolved edge size es
+// (takes ix->mu for the padded adjacency; a.adj null when it does not hold
+// this search's lists), and the planner's view of them (search_plan.h)
+int fill_index_args(ngt_amd_index* ix, uint64_t es, SearchArgs& a);
+PlanShape plan_shape(const ngt_amd_index* ix, const SearchArgs& a);
 // stop and free the serving grid (serve.cpp); no-op without one
 void serve_destroy(ngt_amd_index* ix);
 // stop the serving grid before the index's buffers change: new served calls

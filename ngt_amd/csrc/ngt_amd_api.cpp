@@ -467,39 +467,39 @@ static int ensure_filter(ngt_amd_index* ix) {
   return 0;
 }
 
-// Which search kernel a launch takes: -1 the one-expansion-per-pop kernel
-// (search_kernels.hip; every metric), 0 / 1 the lookahead kernel
-// (search_la.hip; L2 over float rows of 96/128 elements with the padded
-// adjacency) in its throughput (a wave per query) or latency (eight waves per
-// query: launches of under two queries per CU -- single C-API calls,
-// coalesced batches, construction batches) form.  NGT_AMD_LA=0 turns the
-// lookahead kernel off, =1 keeps only the throughput form (for any list
-// length), =2 only latency.
-static int lookahead_mode(const ngt_amd_index* ix, const SearchArgs& a, const ngt_amd_search_params* prm,
-                          uint32_t nq) {
-  const char* ev = ngt_amd::knob("NGT_AMD_LA");
-  const int env = ev ? atoi(ev) : 3;
-  if (env == 0) return -1;
-  if (ix->metric != NGT_AMD_DISTANCE_L2 || ix->otype != NGT_AMD_OBJECT_FLOAT || (ix->dp != 128 && ix->dp != 96))
-    return -1;
-  if (!a.adj || a.adj_stride > 256) return -1;
-  if (prm->distance_filter < 0) return -1;  // the lookahead kernel always filters
-  if (ngt_amd::knob("NGT_AMD_FILTER") && atoi(ngt_amd::knob("NGT_AMD_FILTER")) == 0) return -1;
-  const int mode = nq < 2u * (uint32_t)ix->cu_count ? 1 : 0;
-  // a wave per query pays off on short lists (an NGT index at its
-  // EdgeSizeForSearch of 40: ~4 lists per step); long lists (the C2 kNN graph,
-  // ~136 ids) fill a step with one list, and the one-expansion kernel's
-  // chunk pipeline with 16 waves per CU is faster there
-  const uint64_t deg = std::min<uint64_t>(a.adj_stride, a.edge_size);
-  if (mode == 0 && deg > 64 && env != 1) return -1;
-  if ((env & (1 << mode)) == 0) return -1;
-  return mode;
+// The index's fields of SearchArgs for a search of resolved edge size es: the
+// rows, the CSR lists and the padded copy, when it holds every edge this
+// search reads (grown on demand; a.adj stays null otherwise).
+int ngt_amd::fill_index_args(ngt_amd_index* ix, uint64_t es, SearchArgs& a) {
+  a.rows = ix->rows.p;
+  a.row_bytes = ix->row_bytes;
+  a.nrows = (uint32_t)ix->nrows;
+  a.dp = (int)ix->dp;
+  a.edge_off = ix->edge_off.p;
+  a.edges = ix->edges.p;
+  a.edge_size = es;
+  std::lock_guard<std::mutex> lk(ix->mu);
+  const uint64_t need = adjacency_need(ix, es);
+  if (build_padded_adjacency(ix, need)) return -1;
+  const bool fits = ix->adj.p && need <= ix->adj_stride;
+  a.adj = fits ? ix->adj.p : nullptr;
+  a.adj_stride = fits ? ix->adj_stride : 0;
+  return 0;
 }
 
-// NGT_AMD_SCHED=0: every search one launch in query order
-static int sched_mode() {
-  const char* v = ngt_amd::knob("NGT_AMD_SCHED");
-  return v ? atoi(v) : 1;
+PlanShape ngt_amd::plan_shape(const ngt_amd_index* ix, const SearchArgs& a) {
+  PlanShape sh{};
+  sh.metric = ix->metric;
+  sh.otype = ix->otype;
+  sh.dp = ix->dp;
+  sh.row_bytes = ix->row_bytes;
+  sh.nrows = ix->nrows;
+  sh.cu_count = ix->cu_count;
+  sh.lds_per_block = ix->lds_per_block;
+  sh.lds_per_cu = ix->lds_per_cu;
+  sh.adj_stride = a.adj ? a.adj_stride : 0;
+  sh.edge_size = a.edge_size;
+  return sh;
 }
 
 static uint32_t __float_as_uint_host(float f) {
@@ -523,253 +523,35 @@ static void sched_collect(SearchCtx* c) {
   c->sched_mean.push_back({c->stat_key, mean});
 }
 
-static int run_search(ngt_amd_index* ix, SearchCtx* c, const ngt_amd_search_params* prm, const void* d_queries,
-                      uint64_t query_bytes, uint32_t nq, const uint32_t* d_seeds,
-                      const uint64_t* d_seed_off, uint32_t* d_ids, float* d_dists, uint32_t* d_n,
-                      uint64_t* d_counters, hipStream_t s) {
-  if (!ix->has_graph) return fail("search: the index has no graph");
-  if (prm->k == 0) return fail("search: k must be > 0");
-  uint64_t es = ngt_amd_resolve_edge_size(ix, prm->edge_size, prm->epsilon);
-  if (es == 0) return fail("search: invalid edge size %lld", (long long)prm->edge_size);
-
-  SearchArgs a{};
-  a.rows = ix->rows.p;
-  a.row_bytes = ix->row_bytes;
-  a.nrows = (uint32_t)ix->nrows;
-  a.dp = (int)ix->dp;
-  a.edge_off = ix->edge_off.p;
-  a.edges = ix->edges.p;
-  {
-    // the padded copy, when it holds every edge this search reads
-    const uint64_t need = adjacency_need(ix, es);
-    std::lock_guard<std::mutex> lk(ix->mu);
-    if (build_padded_adjacency(ix, need)) return -1;
-    const bool fits = ix->adj.p && need <= ix->adj_stride;
-    a.adj = fits ? ix->adj.p : nullptr;
-    a.adj_stride = fits ? ix->adj_stride : 0;
-  }
-  if (const char* v = ngt_amd::knob("NGT_AMD_ADJ"))
-    if (atoi(v) == 0) a.adj = nullptr;
-  int la_mode = -1;
-  a.queries = static_cast<const uint8_t*>(d_queries);
-  a.query_bytes = query_bytes;
-  a.nq = nq;
-  a.k = prm->k;
-  a.coef = coef_of(prm->epsilon);
-  a.radius = prm->radius < 0.0f ? FLT_MAX : prm->radius;
-  a.edge_size = es;
-  // LDS capacities of the visited hash and the unchecked array; overridable
-  // (NGT_AMD_HT_LOG2 / NGT_AMD_CQ_CAP) so tests can force the exact HBM
-  // overflow paths.
-  a.ht_log2 = 12;
-  a.cq_cap = 1024;
-  a.vf_log2 = 0;
-  // Small launches (construction batches) leave most of the chip idle and
-  // their time is the slowest query's: give each query a larger LDS visited
-  // hash and unchecked array (57 KB, two per CU) so long searches stay out
-  // of the HBM epochs and the HBM spill.
-  if (nq <= 2048 && prm->visited_hash_log2 == 0) {
-    a.ht_log2 = 13;
-    a.cq_cap = 3072;
-    a.vf_log2 = 15;  // for the long ones that outgrow the hash (61.5 KB in all)
-    a.k = prm->k;
-    if (search_lds_bytes(a, ix->otype) > 64 * 1024) {  // large k: the default sizes
-      a.ht_log2 = 12;
-      a.cq_cap = 1024;
-      a.vf_log2 = 0;
-    }
-    // up to one wave per CU (a construction batch of 200): each query may take
-    // most of its CU's LDS, so the slowest searches -- which decide the batch
-    // time -- keep their visited set and unchecked keys out of HBM (a pop
-    // otherwise rescans the HBM spill: the tail of 1M ANNG construction)
-    if (nq <= (uint32_t)ix->cu_count && ix->lds_per_block >= 128 * 1024) {
-      SearchArgs b = a;
-      b.ht_log2 = 14;
-      b.cq_cap = 8192;
-      b.vf_log2 = 15;
-      if (search_lds_bytes(b, ix->otype) <= ix->lds_per_block) a = b;
-    }
-  }
-  if (prm->visited_hash_log2 < 0) {
-    // HBM-epoch visited set (searches visiting ~1e5 ids, the C2 bench): a
-    // 32 Kbit LDS filter proves most fresh ids unvisited without their HBM
-    // probe, paid for by a 512-key unchecked array (same 9 KB of LDS, 16
-    // waves per CU); measured +8 % QPS on C2 at identical results.
-    // Long rows (C3: 3,840 B) dwarf the 128-B probe and their searches
-    // saturate any LDS-sized filter: epochs alone there.
-    a.ht_log2 = 0;
-    // 512 unchecked keys in LDS (exact HBM spill beyond): C3's long rows then
-    // fit 16 waves per CU instead of 11 (+6 % QPS).  Long cosine/angle rows
-    // run at 12 waves per CU (search_kernels.hip), whose LDS holds 768: 794
-    // vs 808 ms per C3 launch (profiles/r5zk)
-    a.cq_cap = 512;
-    if (ix->row_bytes > 1024 && ix->otype == NGT_AMD_OBJECT_FLOAT &&
-        (ix->metric == NGT_AMD_DISTANCE_COSINE || ix->metric == NGT_AMD_DISTANCE_ANGLE))
-      a.cq_cap = 768;
-    if (ix->row_bytes <= 1024) {
-      a.vf_log2 = 15;
-      // -2: the filter and epochs hold accepted ids only (a few thousand per
-      // query instead of ~7e4), so the filter stays sparse and almost no
-      // neighbour costs an HBM probe or a mark store; rejected neighbours met
-      // again are re-evaluated (search_common.h: not_accepted).  C2: +33 % QPS
-      // at identical results for +14 % distance evaluations.
-      a.accepted_only = prm->visited_hash_log2 == -2;
-    }
-  }
-  else if (prm->visited_hash_log2 > 0) a.ht_log2 = (uint32_t)std::max(8, std::min(15, prm->visited_hash_log2));
-  if (const char* v = ngt_amd::knob("NGT_AMD_HT_LOG2")) a.ht_log2 = (uint32_t)std::max(8, std::min(15, atoi(v)));
-  if (const char* v = ngt_amd::knob("NGT_AMD_CQ_CAP")) a.cq_cap = (uint32_t)std::max(64, std::min(8192, atoi(v)));
-  if (const char* v = ngt_amd::knob("NGT_AMD_ACCEPTED_ONLY")) a.accepted_only = atoi(v) != 0;
-  if (const char* v = ngt_amd::knob("NGT_AMD_VFILTER")) {
-    const int f = atoi(v);
-    a.vf_log2 = f <= 0 ? 0u : (uint32_t)std::max(11, std::min(18, f));
-  }
-  a.out_ids = d_ids;
-  a.out_dists = d_dists;
-  a.out_n = d_n;
-  a.counters = d_counters;
-  a.error = c->err.p;
-  // 1-byte filter copy for throughput launches over L2 float rows of 96/128
-  // elements: a neighbour the bound places outside the exploration radius
-  // costs Dp bytes instead of 4 Dp (filter_kernels.hip); latency-bound small
-  // launches (construction batches) skip it, since a surviving neighbour then
-  // costs a second round trip.  NGT_AMD_FILTER=0/1 forces it off/on.
-  {
-    static const int force = [] {
-      const char* v = ngt_amd::knob("NGT_AMD_FILTER");
-      return v ? atoi(v) : -1;
-    }();
-    // L2 rows of 96/128 floats (integer bound, pipelined expansion) or
-    // cosine/angle long rows (streamed comparator; search_common.h filter_cos_u8)
-    const bool shape = ix->otype == NGT_AMD_OBJECT_FLOAT &&
-                       ((ix->metric == NGT_AMD_DISTANCE_L2 && (ix->dp == 128 || ix->dp == 96)) ||
-                        ((ix->metric == NGT_AMD_DISTANCE_COSINE || ix->metric == NGT_AMD_DISTANCE_ANGLE) &&
-                         ix->dp > 128 && ix->dp % 64 == 0 && !ngt_amd::knob("NGT_AMD_NO_STREAM")));
-    const bool want = force >= 0 ? force != 0
-                                 : (prm->distance_filter != 0 ? prm->distance_filter > 0
-                                                              : nq >= 2u * (uint32_t)ix->cu_count);
-    // the lookahead kernel (search_la.hip) shares one filter round trip
-    // among a step's expansions, so it takes the filter at every launch size
-    la_mode = lookahead_mode(ix, a, prm, nq);
-    if (shape && (want || la_mode >= 0)) {
-      if (ensure_filter(ix)) return -1;
-      a.fcodes = ix->filt.codes.p;
-      a.fstride = ix->filt.stride;
-      a.fparams = ix->filt.params.p;
-    }
-    c->launch_filtered = a.fcodes != nullptr;
-    if (!a.fcodes) la_mode = -1;
-  }
-  if (la_mode >= 0) {
-    // one step's target lists (<= 256 ids each) and the exact per-step id set
-    static const uint32_t env_lmax = [] {
-      const char* v = ngt_amd::knob("NGT_AMD_LA_LMAX");
-      return v ? (uint32_t)std::max(256, std::min(8192, atoi(v))) : 0u;
-    }();
-    // list capacity: the targets' lists of the longest kind (t0's always fits)
-    const uint32_t deg_cap = (uint32_t)std::min<uint64_t>(a.adj_stride, a.edge_size);
-    const uint32_t P = la_targets(la_mode);
-    a.la_lmax = env_lmax ? env_lmax
-                         : (la_mode == 0 ? std::max<uint32_t>(deg_cap, std::min<uint32_t>(256u, (P * deg_cap + 15) & ~15u))
-                                         : 2048u);
-    a.la_lmax = std::max<uint32_t>(a.la_lmax, deg_cap);
-    // per-step id set: twice the ids a step can insert -- every list entry
-    // with the full visited set; the accepted-only set inserts only accepted
-    // ids, and the commit loop stops before a target could overfill it, so
-    // there 4 x the longest list is plenty (and keeps 12 waves per CU)
-    const uint32_t sh_want = (la_mode == 0 && a.accepted_only) ? std::min<uint32_t>(2u * a.la_lmax, 4u * deg_cap)
-                                                               : 2u * a.la_lmax;
-    a.la_sh_log2 = 1;
-    while ((1u << a.la_sh_log2) < sh_want) a.la_sh_log2++;
-    if (a.vf_log2 == 0) a.vf_log2 = 15;
-    a.cq_cap = la_mode == 0 ? 512u : 2048u;
-    if (la_mode == 0 && la_wpe() == 4) {
-      a.vf_log2 = 14;
-      a.cq_cap = 256u;
-    }
-    if (const char* v = ngt_amd::knob("NGT_AMD_CQ_CAP")) a.cq_cap = (uint32_t)std::max(64, std::min(8192, atoi(v)));
-    if (const char* v = ngt_amd::knob("NGT_AMD_VFILTER"))
-      if (atoi(v) > 0) a.vf_log2 = (uint32_t)std::max(11, std::min(18, atoi(v)));
-  }
-
-  if (prm->seed_mode == NGT_AMD_SEED_TREE) {
-    if (run_tree_seeds(ix, c, d_queries, query_bytes, nq, prm->k, prm->all_leaf_nodes, s)) return -1;
-    a.seeds = c->seeds.p;
-    a.seed_stride = kTreeSeedStride;
-    a.seed_count = c->seed_count.p;
-  } else {
-    if (!d_seeds || !d_seed_off) return fail("search: seed lists required for this seed mode");
-    a.seeds = d_seeds;
-    a.seed_off = d_seed_off;
-  }
-  const size_t lds_max = std::max<size_t>(64 * 1024, std::min<size_t>(ix->lds_per_block, ix->lds_per_cu));
-  // latency launches: the speculating kernel (search_lat.hip) when the exact
-  // LDS visited bitmap of every object fits one CU's LDS with its slots
-  bool lat = false;
-  if (la_mode == 1) {
-    static const bool lat_on = [] {
-      const char* v = ngt_amd::knob("NGT_AMD_LAT");
-      return !v || atoi(v) != 0;
-    }();
-    const uint32_t cap = (uint32_t)std::min<uint64_t>(a.adj_stride, a.edge_size);
-    if (lat_on && a.adj && cap <= 256u && a.k <= 64u) {  // lists of <= 256 ids, results in one wave's registers
-      SearchArgs b = a;
-      b.lat_slots = cap <= 64 ? 32u : 16u;
-      b.lat_tail = 4096u;
-      b.lat_hop = lat_hop_default();
-      b.lat_feed = lat_feed_default();
-      while (search_lat_lds_bytes(b) > lds_max && b.lat_tail > 512u) b.lat_tail -= 256u;
-      while (search_lat_lds_bytes(b) > lds_max && b.lat_slots > 8u) b.lat_slots -= 2u;
-      // test knobs: a small tail forces the HBM spill, few slots the orphan path
-      if (const char* v = ngt_amd::knob("NGT_AMD_LAT_TAIL")) b.lat_tail = (uint32_t)std::max(128, std::min(4096, atoi(v)));
-      if (const char* v = ngt_amd::knob("NGT_AMD_LAT_SLOTS")) b.lat_slots = (uint32_t)std::max(2, std::min(64, atoi(v)));
-      if (search_lat_lds_bytes(b) <= lds_max) {
-        a = b;
-        lat = true;
-      }
-    }
-  }
-  if (!lat && la_mode >= 0 && search_la_lds_bytes(a, (int)la_targets(la_mode)) > lds_max) la_mode = -1;  // large k
-  const size_t lds = lat ? search_lat_lds_bytes(a)
-                         : la_mode >= 0 ? search_la_lds_bytes(a, (int)la_targets(la_mode)) : search_lds_bytes(a, ix->otype);
-  if (lds > lds_max) return fail("search: k=%u needs %zu bytes of LDS per query (max %zu)", a.k, lds, lds_max);
-  if (ensure_vis_scratch(ix, c, lds, nq, s)) return -1;
-  a.vis = c->vis.p;
-  a.vis_stride = c->vis_stride;
-  a.slot_epoch = c->slot_epoch.p;
-  a.spill = c->spill.p;
-  a.spill_cap = ix->spill_cap;
-  a.work = c->work.p;
-  HIP_OK(hipMemsetAsync(c->work.p, 0, 3 * sizeof(uint32_t), s));
-  uint32_t slots = std::min<uint32_t>(c->slots, nq);
-  c->launch_slots = slots;
-  c->launch_la = la_mode;
-  // ---- launch schedule: "probe and resume" ------------------------------
-  // A launch's time is its slowest slot's: with ~2.4 queries per slot, a long
-  // search that happens to start last decides it (C2: 22.1 ms in query order,
-  // 16.6 ms longest-first with the true costs, profiles/r4d).  Cheap query
-  // features do not predict the cost (centroid distance, sampled distance
-  // contrast: rank correlation < 0.1); the search's own state does: the
-  // unchecked keys within the exploration radius after part of the search.
-  // So a probe launch runs every query for B expansions (B = 0.25 x the mean
-  // expansions per query of earlier launches of this configuration) and
-  // pauses the unfinished ones with their state saved; a one-workgroup
-  // counting sort orders them by that count; a resume launch continues them
-  // in that order.  Accepted-only visited sets only (the resume rebuilds the
-  // set from the popped ids and the unchecked keys; search_kernels.hip), so
-  // the results, distance bits and expansion counts are the single
-  // launch's.  Measured (profiles/r4e, r4f): C2 22.2 -> 18.6 ms per 10k-query
-  // search at 0.12 (19.4 at 0.25, 20.2 at 0.4) on the kNN128 graph; on the
-  // denser kNN256 graph (327 expansions per query, profiles/r5o, r5p) 16.3 /
-  // 16.2 / 15.4 / 15.4 / 15.1 / 15.3 ms at 0.06 / 0.12 / 0.2 / 0.25 / 0.3 /
-  // 0.4.  The lookahead kernel (the ANNG's short lists) took the same scheme
-  // and ran slower at every fraction (0.08-0.5: 164-174 ms against 156), so
-  // it is not scheduled.
-  const bool sched_shape = !lat && la_mode < 0 && a.accepted_only && a.ht_log2 == 0 && a.vf_log2 != 0 && a.adj &&
-                           a.fcodes && a.k <= 64;
+// The planned kernel's launch between c->ev0 and c->ev1, split in two where
+// the plan allows and a budget is known:
+// ---- launch schedule: "probe and resume" ------------------------------
+// A launch's time is its slowest slot's: with ~2.4 queries per slot, a long
+// search that happens to start last decides it (C2: 22.1 ms in query order,
+// 16.6 ms longest-first with the true costs, profiles/r4d).  Cheap query
+// features do not predict the cost (centroid distance, sampled distance
+// contrast: rank correlation < 0.1); the search's own state does: the
+// unchecked keys within the exploration radius after part of the search.
+// So a probe launch runs every query for B expansions (B = 0.25 x the mean
+// expansions per query of earlier launches of this configuration) and
+// pauses the unfinished ones with their state saved; a one-workgroup
+// counting sort orders them by that count; a resume launch continues them
+// in that order.  Accepted-only visited sets only (the resume rebuilds the
+// set from the popped ids and the unchecked keys; search_kernels.hip), so
+// the results, distance bits and expansion counts are the single
+// launch's.  Measured (profiles/r4e, r4f): C2 22.2 -> 18.6 ms per 10k-query
+// search at 0.12 (19.4 at 0.25, 20.2 at 0.4) on the kNN128 graph; on the
+// denser kNN256 graph (327 expansions per query, profiles/r5o, r5p) 16.3 /
+// 16.2 / 15.4 / 15.4 / 15.1 / 15.3 ms at 0.06 / 0.12 / 0.2 / 0.25 / 0.3 /
+// 0.4.  The lookahead kernel (the ANNG's short lists) took the same scheme
+// and ran slower at every fraction (0.08-0.5: 164-174 ms against 156), so
+// it is not scheduled (search_plan.cpp: sched_shape).
+static int launch_planned(ngt_amd_index* ix, SearchCtx* c, const SearchPlan& plan, SearchArgs& a,
+                               uint32_t slots, hipStream_t s) {
+  const uint32_t nq = a.nq;
   uint32_t budget = 0;
   uint64_t skey = 0;
-  if (sched_shape && sched_mode() != 0) {
+  if (plan.sched_on) {
     skey = (uint64_t)a.edge_size * 0x9E3779B97F4A7C15ull ^ ((uint64_t)__float_as_uint_host(a.coef) << 17) ^
            ((uint64_t)a.k << 49) ^ (ix->rows_version * 0xC2B2AE3D27D4EB4Full) ^ (ix->adj_version << 7) ^
            ((uint64_t)a.cq_cap << 33);
@@ -777,16 +559,10 @@ static int run_search(ngt_amd_index* ix, SearchCtx* c, const ngt_amd_search_para
     double mean = 0.0;
     for (auto& m : c->sched_mean)
       if (m.first == skey) mean = m.second;
-    static const double frac = [] {
-      const char* v = ngt_amd::knob("NGT_AMD_SCHED_FRAC");
-      return v ? std::max(0.01, std::min(0.9, atof(v))) : 0.25;
-    }();
-    // test knob: a fixed budget for every eligible launch
-    const int forced = ngt_amd::knob("NGT_AMD_SCHED_B") ? std::max(0, atoi(ngt_amd::knob("NGT_AMD_SCHED_B"))) : 0;
-    if (forced) budget = (uint32_t)forced;
-    else if (mean > 0.0) budget = (uint32_t)std::max(8.0, mean * frac);
+    if (plan.sched_forced) budget = plan.sched_forced;
+    else if (mean > 0.0) budget = (uint32_t)std::max(8.0, mean * plan.sched_frac);
     // a tail needs more queries than slots (forced: any launch, for tests)
-    if (!forced && (uint64_t)nq * 4 < (uint64_t)slots * 5) budget = 0;
+    if (!plan.sched_forced && (uint64_t)nq * 4 < (uint64_t)slots * 5) budget = 0;
   }
   if (budget) {
     // the paused queries' records (~17 KB per query at cq_cap 1024) must fit
@@ -806,17 +582,16 @@ static int run_search(ngt_amd_index* ix, SearchCtx* c, const ngt_amd_search_para
     }
   }
   c->launch_budget = budget;
-  if (sched_shape) {
+  if (plan.sched_shape) {
     HIP_OK(c->stat.alloc(2));
     HIP_OK(hipMemsetAsync(c->stat.p, 0, 2 * sizeof(unsigned long long), s));
     a.stat = c->stat.p;
   }
   HIP_OK(hipEventRecord(c->ev0, s));
-  if (lat) {
+  if (plan.kernel == kPlanSpeculating) {
     HIP_OK(launch_graph_search_lat(a, slots, s));
-  } else if (la_mode >= 0) {
-    // full visited set unless the caller asked for the accepted-only one
-    HIP_OK(launch_graph_search_la(a, la_mode, !a.accepted_only, slots, s));
+  } else if (plan.kernel != kPlanOneExpansion) {
+    HIP_OK(launch_graph_search_la(a, plan.la_mode(), plan.la_full, slots, s));
   } else if (budget) {
     const PauseLayout lay(a.k, a.cq_cap, budget);
     HIP_OK(c->qstate.alloc((size_t)nq * lay.total));
@@ -843,7 +618,7 @@ static int run_search(ngt_amd_index* ix, SearchCtx* c, const ngt_amd_search_para
     HIP_OK(launch_graph_search(a, ix->metric, ix->otype, slots, s));
   }
   HIP_OK(hipEventRecord(c->ev1, s));
-  if (sched_shape) {
+  if (plan.sched_shape) {
     // this launch's mean expansions per query, for the next launch's budget
     if (!c->h_stat) HIP_OK(hipHostMalloc((void**)&c->h_stat, 2 * sizeof(unsigned long long), hipHostMallocDefault));
     if (!c->ev_stat) HIP_OK(hipEventCreateWithFlags(&c->ev_stat, hipEventDisableTiming));
@@ -853,6 +628,75 @@ static int run_search(ngt_amd_index* ix, SearchCtx* c, const ngt_amd_search_para
     c->stat_key = skey;
   }
   return 0;
+}
+
+// One graph search: plan it (search_plan.cpp decides the kernel and every LDS
+// capacity), then gather what the plan needs and launch.
+static int run_search(ngt_amd_index* ix, SearchCtx* c, const ngt_amd_search_params* prm, const void* d_queries,
+                      uint64_t query_bytes, uint32_t nq, const uint32_t* d_seeds,
+                      const uint64_t* d_seed_off, uint32_t* d_ids, float* d_dists, uint32_t* d_n,
+                      uint64_t* d_counters, hipStream_t s) {
+  if (!ix->has_graph) return fail("search: the index has no graph");
+  if (prm->k == 0) return fail("search: k must be > 0");
+  uint64_t es = ngt_amd_resolve_edge_size(ix, prm->edge_size, prm->epsilon);
+  if (es == 0) return fail("search: invalid edge size %lld", (long long)prm->edge_size);
+
+  SearchArgs a{};
+  if (fill_index_args(ix, es, a)) return -1;
+  const SearchPlan plan = plan_search(plan_shape(ix, a), *prm, nq, read_plan_knobs());
+  if (!plan.use_adj) a.adj = nullptr;
+  a.queries = static_cast<const uint8_t*>(d_queries);
+  a.query_bytes = query_bytes;
+  a.nq = nq;
+  a.k = prm->k;
+  a.coef = coef_of(prm->epsilon);
+  a.radius = prm->radius < 0.0f ? FLT_MAX : prm->radius;
+  a.ht_log2 = plan.ht_log2;
+  a.cq_cap = plan.cq_cap;
+  a.vf_log2 = plan.vf_log2;
+  a.accepted_only = plan.accepted_only;
+  a.la_lmax = plan.la_lmax;
+  a.la_sh_log2 = plan.la_sh_log2;
+  a.lat_slots = plan.lat_slots;
+  a.lat_tail = plan.lat_tail;
+  a.lat_hop = plan.lat_hop;
+  a.lat_feed = plan.lat_feed;
+  a.out_ids = d_ids;
+  a.out_dists = d_dists;
+  a.out_n = d_n;
+  a.counters = d_counters;
+  a.error = c->err.p;
+  if (plan.use_filter) {
+    if (ensure_filter(ix)) return -1;
+    a.fcodes = ix->filt.codes.p;
+    a.fstride = ix->filt.stride;
+    a.fparams = ix->filt.params.p;
+  }
+  c->launch_filtered = plan.use_filter;
+
+  if (prm->seed_mode == NGT_AMD_SEED_TREE) {
+    if (run_tree_seeds(ix, c, d_queries, query_bytes, nq, prm->k, prm->all_leaf_nodes, s)) return -1;
+    a.seeds = c->seeds.p;
+    a.seed_stride = kTreeSeedStride;
+    a.seed_count = c->seed_count.p;
+  } else {
+    if (!d_seeds || !d_seed_off) return fail("search: seed lists required for this seed mode");
+    a.seeds = d_seeds;
+    a.seed_off = d_seed_off;
+  }
+  if (!plan.error.empty()) return fail("%s", plan.error.c_str());
+  if (ensure_vis_scratch(ix, c, plan.lds_bytes, nq, s)) return -1;
+  a.vis = c->vis.p;
+  a.vis_stride = c->vis_stride;
+  a.slot_epoch = c->slot_epoch.p;
+  a.spill = c->spill.p;
+  a.spill_cap = ix->spill_cap;
+  a.work = c->work.p;
+  HIP_OK(hipMemsetAsync(c->work.p, 0, 3 * sizeof(uint32_t), s));
+  const uint32_t slots = std::min<uint32_t>(c->slots, nq);
+  c->launch_slots = slots;
+  c->launch_la = plan.la_mode();
+  return launch_planned(ix, c, plan, a, slots, s);
 }
 
 // The rand() stream getRandomSeeds draws from.  The reference calls the

@@ -101,7 +101,7 @@ struct SearchArgs {
   uint32_t lat_tail;
   uint32_t lat_hop;              // latency kernel: warm L2 for the nearest fresh neighbour of each list part
   uint32_t lat_feed;             // latency kernel: head entries kept speculated (0: 16; capped by lat_slots)
-  // launch schedule (ngt_amd_api.cpp run_search, "probe and resume"): the
+  // launch schedule (ngt_amd_api.cpp launch_planned, "probe and resume"): the
   // w-th work item a slot claims is query order[w] (null: w), and a launch
   // has *nwork_dev work items (null: nq).  A probe launch (pause_after > 0)
   // pauses every query after pause_after expansions: its state goes to
@@ -213,20 +213,7 @@ inline uint32_t la_targets(int mode) {
 // workgroups fit a CU; ANNG 72.0k QPS) or 3 (168 VGPRs, 6 groups, 512 keys,
 // 32 Kbit; 64.7k QPS): 4
 inline int la_wpe() { return 4; }
-// latency kernel: hop prefetch of each list part's nearest fresh neighbour
-// (search_lat.hip); NGT_AMD_LAT_HOP=0 turns it off (A/B)
-// (read per launch, so a test process can compare both forms)
-inline uint32_t lat_hop_default() {
-  const char* e = ngt_amd::knob("NGT_AMD_LAT_HOP");
-  return e ? (atoi(e) != 0 ? 1u : 0u) : 1u;
-}
-// latency kernel: head entries kept speculated; NGT_AMD_LAT_FEED=n (A/B)
-inline uint32_t lat_feed_default() {
-  const char* e = ngt_amd::knob("NGT_AMD_LAT_FEED");
-  return e ? (uint32_t)std::max(1, std::min(64, atoi(e))) : 0u;
-}
-uint32_t search_la_lds_bytes(const SearchArgs& a, int P);
-uint32_t search_lat_lds_bytes(const SearchArgs& a);
+// (the kernels' LDS sizes: search_layout.h; the launch planning: search_plan.h)
 hipError_t launch_graph_search_lat(const SearchArgs& a, uint32_t slots, hipStream_t s);
 hipError_t launch_graph_serve_lat(const SearchArgs& a, const ServeArgs& sv, hipStream_t s);
 hipError_t launch_graph_search_la(const SearchArgs& a, int mode, bool full, uint32_t slots, hipStream_t s);
@@ -336,7 +323,6 @@ hipError_t launch_pack_results(const uint32_t* ids, const float* dists, const ui
                                uint64_t* out, hipStream_t s);
 hipError_t launch_merge_packed(const MergeArgs& a, const uint64_t* packed, hipStream_t s);
 hipError_t launch_tree_seeds(const TreeSeedArgs& a, int metric, int otype, hipStream_t s);
-size_t search_lds_bytes(const SearchArgs& a, int otype);
 // the resume launch's order: paused queries (qflag 1) by descending prio
 hipError_t launch_schedule(const uint32_t* qflag, const float* prio, uint32_t nq, uint32_t* order, uint32_t* n_out,
                            hipStream_t s);

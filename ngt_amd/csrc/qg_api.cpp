@@ -430,12 +430,7 @@ extern "C" int ngt_amd_qg_search_device(ngt_amd_index* ix, const ngt_amd_qg_sear
     a.vf_log2 = 15;
   }
   else if (prm->visited_hash_log2 > 0) a.ht_log2 = (uint32_t)std::max(8, std::min(15, prm->visited_hash_log2));
-  if (const char* v = ngt_amd::knob("NGT_AMD_HT_LOG2")) a.ht_log2 = (uint32_t)std::max(8, std::min(15, atoi(v)));
-  if (const char* v = ngt_amd::knob("NGT_AMD_CQ_CAP")) a.cq_cap = (uint32_t)std::max(64, std::min(8192, atoi(v)));
-  if (const char* v = ngt_amd::knob("NGT_AMD_VFILTER")) {
-    const int f = atoi(v);
-    a.vf_log2 = f <= 0 ? 0u : (uint32_t)std::max(11, std::min(18, f));
-  }
+  apply_visited_knobs(read_plan_knobs(), a.ht_log2, a.cq_cap, a.vf_log2);
   a.out_ids = d_ids;
   a.out_dists = d_dists;
   a.out_n = d_n;

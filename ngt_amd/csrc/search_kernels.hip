@@ -28,6 +28,7 @@
 #include "ngt_device.h"
 #include "ngt_kernels.h"
 #include "search_common.h"
+#include "search_layout.h"
 
 namespace ngt_amd {
 
@@ -950,17 +951,6 @@ hipError_t launch_tree_seeds(const TreeSeedArgs& a, int metric, int otype, hipSt
   NGT_DISPATCH(metric, otype, L_TREE);
 #undef L_TREE
   return hipGetLastError();
-}
-
-size_t search_lds_bytes(const SearchArgs& a, int otype) {
-  size_t b = (a.ht_log2 ? ((size_t)4 << a.ht_log2) : 0) + (size_t)8 * a.cq_cap;
-  b += ((size_t)8 * ((a.cq_cap + 63) / 64) + 15) & ~(size_t)15;  // chunk minima
-  b += a.vf_log2 ? ((size_t)1 << a.vf_log2) / 8 : 0;
-  b += ((size_t)8 * (a.k + 1) + 15) & ~(size_t)15;
-  b += 512;
-  b += ((size_t)a.dp * (otype == kFloat ? 4 : 1) + 15) & ~(size_t)15;
-  if (a.fcodes) b += (size_t)a.dp + 256;  // the query's filter bytes and the pending survivors
-  return b;
 }
 
 // Launch schedule of the resume launch: the queries the probe launch paused

@@ -37,44 +37,9 @@
 #include "ngt_device.h"
 #include "ngt_kernels.h"
 #include "search_common.h"
+#include "search_layout.h"
 
 namespace ngt_amd {
-
-struct LaCtl {
-  uint32_t qi, done, nt, ntl, nl, nx, fthr, fsq;
-  uint32_t epoch, pad[7];
-  // the filter threshold's double-precision terms, kept in LDS: in registers
-  // they spill, and a scratch reload waits for every store still in flight
-  double fe, finv_b, frq;
-};
-
-// 16-byte aligned LDS carve-out; the host's search_la_lds_bytes mirrors it.
-struct LaLayout {
-  uint32_t off_tkey, off_tcnt, off_loff, off_xoff, off_vf, off_cq, off_res, off_q, off_qb, off_l,
-      off_lfl, off_x, off_xe, off_xd, off_sh, off_nid, off_nd, total;
-  __host__ __device__ static uint32_t up16(uint32_t v) { return (v + 15u) & ~15u; }
-  __host__ __device__ LaLayout(const SearchArgs& a, int P) {
-    uint32_t o = up16(sizeof(LaCtl));
-    off_tkey = o; o = up16(o + 8u * P);
-    off_tcnt = o; o = up16(o + 4u * P);
-    off_loff = o; o = up16(o + 4u * (P + 1));
-    off_xoff = o; o = up16(o + 4u * (P + 1));
-    off_vf = o; o = up16(o + ((1u << a.vf_log2) >> 3));
-    off_cq = o; o = up16(o + 8u * a.cq_cap);
-    off_res = o; o = up16(o + 8u * (a.k + 1));
-    off_q = o; o = up16(o + 4u * (uint32_t)a.dp);
-    off_qb = o; o = up16(o + (uint32_t)a.dp);
-    off_l = o; o = up16(o + 4u * a.la_lmax);
-    off_lfl = o; o = up16(o + a.la_lmax);
-    off_x = o; o = up16(o + 4u * a.la_lmax);
-    off_xe = o; o = up16(o + 4u * a.la_lmax);
-    off_xd = o; o = up16(o + 4u * a.la_lmax);
-    off_sh = o; o = up16(o + (4u << a.la_sh_log2));
-    off_nid = o; o = up16(o + 256u);
-    off_nd = o; o = up16(o + 256u);
-    total = o;
-  }
-};
 
 // exact per-step set of ids (open addressing, 0 = empty)
 __device__ __forceinline__ uint32_t sh_slot(uint32_t id, uint32_t log2) { return (id * 0x9E3779B1u) >> (32 - log2); }
@@ -1012,8 +977,6 @@ ngt_graph_search_la_kernel(SearchArgs a) {
     __syncthreads();
   }
 }
-
-uint32_t search_la_lds_bytes(const SearchArgs& a, int P) { return LaLayout(a, P).total; }
 
 // mode 0: throughput (W = 1), mode 1: latency (W = 8)
 hipError_t launch_graph_search_la(const SearchArgs& a, int mode, bool full, uint32_t slots, hipStream_t s) {

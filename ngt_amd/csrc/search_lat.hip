@@ -33,6 +33,7 @@
 #include "ngt_device.h"
 #include "ngt_kernels.h"
 #include "search_common.h"
+#include "search_layout.h"
 
 namespace ngt_amd {
 
@@ -40,50 +41,6 @@ namespace {
 
 constexpr uint32_t kNoTag = 0xffu;  // head entry without a slot
 constexpr uint32_t kFree = 0u, kIssued = 1u;
-
-struct LatCtl {
-  uint32_t done;  // the commit wave has finished the query
-  uint32_t qi;
-  uint32_t quit;  // serving form: no more work for this workgroup
-  uint32_t k;     // this query's SearchContainer::size, coefficient, radius
-  float coef;
-  float radius;
-  float expr;     // the commit wave's exploration radius (read by the hop prefetch)
-  uint32_t ns;    // serving form: seeds staged in the tail
-  uint64_t sp[4]; // diagnostic build: speculation-wave cycles ([0] adjacency, [2] exact rows)
-};
-
-// one node's speculation: key (its unchecked-set key, the priority), state,
-// the claim word of its list parts (generation << 8 | parts taken), parts
-// finished, list length, fresh entries per part
-struct LatSlot {
-  uint64_t key;
-  uint32_t state;
-  uint32_t claim;
-  uint32_t pready; // parts finished (bit p: part p's entries and count are final)
-  uint32_t deg;    // list length read (getEdgeSize cap), summed over the parts
-  uint32_t pn[8];  // neighbours not yet visited when the part was read
-};
-
-struct LatLayout {
-  uint32_t off_slot, off_eid, off_ed, off_tail, off_q, off_nid, off_nd, off_hist, off_bm,
-      total;
-  __host__ __device__ static uint32_t up16(uint32_t v) { return (v + 15u) & ~15u; }
-  __host__ __device__ LatLayout(const SearchArgs& a, uint32_t cap, uint32_t waves) {
-    uint32_t o = up16(sizeof(LatCtl));
-    const uint32_t ns = a.lat_slots;
-    off_slot = o; o = up16(o + sizeof(LatSlot) * ns);
-    off_eid = o; o = up16(o + 4u * ns * cap);
-    off_ed = o; o = up16(o + 4u * ns * cap);
-    off_tail = o; o = up16(o + 8u * a.lat_tail);
-    off_q = o; o = up16(o + 4u * (uint32_t)a.dp);
-    off_nid = o; o = up16(o + 256u);
-    off_nd = o; o = up16(o + 256u);
-    off_hist = o; o = up16(o + 256u);
-    off_bm = o; o = up16(o + 4u * ((a.nrows + 31u) / 32u));
-    total = o;
-  }
-};
 
 __device__ __forceinline__ bool bm_test(const uint32_t* bm, uint32_t id) { return (bm[id >> 5] >> (id & 31)) & 1u; }
 
@@ -994,11 +951,6 @@ __global__ void __launch_bounds__(64 * W) ngt_graph_search_lat_kernel(SearchArgs
 }  // namespace ngt_amd
 
 namespace ngt_amd {
-
-uint32_t search_lat_lds_bytes(const SearchArgs& a) {
-  const uint32_t cap = (uint32_t)(a.adj_stride < a.edge_size ? a.adj_stride : a.edge_size);
-  return LatLayout(a, cap, 8).total;
-}
 
 hipError_t launch_graph_search_lat(const SearchArgs& a, uint32_t slots, hipStream_t s) {
   if (a.nq == 0) return hipSuccess;

@@ -50,7 +50,7 @@ namespace {
 bool serve_enabled() {
   static const bool on = [] {
     const char* v = ngt_amd::knob("NGT_AMD_SERVE");
-    const char* l = ngt_amd::knob("NGT_AMD_LAT");
+    const char* l = read_plan_knobs().lat;
     return !(v && atoi(v) == 0) && !(l && atoi(l) == 0);
   }();
   return on;
@@ -230,35 +230,18 @@ int serve_args(ngt_amd_index* ix, const ngt_amd_search_params* prm, SearchArgs& 
   const uint64_t es = ngt_amd_resolve_edge_size(ix, prm->edge_size, prm->epsilon);
   if (es == 0) return 1;
   a = SearchArgs{};
-  {
-    std::lock_guard<std::mutex> lk(ix->mu);
-    const uint64_t need = adjacency_need(ix, es);
-    if (build_padded_adjacency(ix, need)) return -1;
-    if (!ix->adj.p || need > ix->adj_stride) return 1;
-    a.adj = ix->adj.p;
-    a.adj_stride = ix->adj_stride;
-  }
+  if (fill_index_args(ix, es, a)) return -1;
+  if (!a.adj) return 1;
   const uint32_t cap = (uint32_t)std::min<uint64_t>(a.adj_stride, es);
   if (cap > 256u) return 1;
-  a.rows = ix->rows.p;
-  a.row_bytes = ix->row_bytes;
-  a.nrows = (uint32_t)ix->nrows;
-  a.dp = (int)ix->dp;
-  a.edge_off = ix->edge_off.p;
-  a.edges = ix->edges.p;
-  a.edge_size = es;
   a.k = prm->k;
-  // the batch latency launch's LDS sizing (ngt_amd_api.cpp run_search)
-  const size_t lds_max = std::max<size_t>(64 * 1024, std::min<size_t>(ix->lds_per_block, ix->lds_per_cu));
-  a.lat_slots = cap <= 64 ? 32u : 16u;
-  a.lat_tail = 4096u;
-  a.lat_hop = lat_hop_default();
-  a.lat_feed = lat_feed_default();
-  while (search_lat_lds_bytes(a) > lds_max && a.lat_tail > 512u) a.lat_tail -= 256u;
-  while (search_lat_lds_bytes(a) > lds_max && a.lat_slots > 8u) a.lat_slots -= 2u;
-  if (const char* v = ngt_amd::knob("NGT_AMD_LAT_TAIL")) a.lat_tail = (uint32_t)std::max(128, std::min(4096, atoi(v)));
-  if (const char* v = ngt_amd::knob("NGT_AMD_LAT_SLOTS")) a.lat_slots = (uint32_t)std::max(2, std::min(64, atoi(v)));
-  if (search_lat_lds_bytes(a) > lds_max) return 1;
+  // the batch latency launch's LDS sizing (search_plan.cpp plan_speculating)
+  SearchPlan plan;
+  if (!plan_speculating(plan_shape(ix, a), a.k, read_plan_knobs(), plan)) return 1;
+  a.lat_slots = plan.lat_slots;
+  a.lat_tail = plan.lat_tail;
+  a.lat_hop = plan.lat_hop;
+  a.lat_feed = plan.lat_feed;
   cfg = ServeConfig{};
   cfg.rows = ix->rows.p;
   cfg.adj = a.adj;
