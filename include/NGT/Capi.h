@@ -42,7 +42,8 @@
  *
  * Extensions (not in the reference): ngt_batch_search_index*,
  * ngt_get_last_search_counters, ngt_get_coalesce_stats, ngt_get_device_index,
- * ngt_optimizer_set_shortcut_reduction, ngt_optimizer_get.
+ * ngt_optimizer_set_shortcut_reduction, ngt_optimizer_get,
+ * ngt_batch_remove_index.
  */
 #ifndef NGT_AMD_CAPI_H
 #define NGT_AMD_CAPI_H
@@ -217,6 +218,12 @@ bool ngt_get_coalesce_stats(NGTIndex, uint64_t *batches, uint64_t *served, NGTEr
  * batched device-pointer searches on an index opened or built through this
  * API.  Owned by the handle; valid until the next write to it or its close. */
 void *ngt_get_device_index(NGTIndex, NGTError);
+/* NGT::Index::remove(database, ids) (lib/NGT/Index.cpp:235-252) without the
+ * open and the save: ngt_remove_index of ids[0..n) in order, in one device
+ * session.  An id the reference would pass over with a warning (no such
+ * object, or a graph inconsistency) is passed over here too: removed[i]
+ * (nullable) = 1 when ids[i] was removed, and the call still returns true. */
+bool ngt_batch_remove_index(NGTIndex, const uint32_t *ids, size_t n, uint8_t *removed, NGTError);
 
 #ifdef __cplusplus
 }

@@ -20,9 +20,9 @@
  *   NGT::ObjectDistances lib/NGT/ObjectSpace.h:26-91
  *   NGT::ObjectSpace     lib/NGT/ObjectSpace.h:146-292 (enums, getObject)
  *
- * Errors surface as NGT::Exception carrying the C API's message.  Entry points
- * of graph maintenance (remove) and graph-only construction throw: they are
- * outside this build's scope.  The ONNG reconstruction is NGT::GraphOptimizer
+ * Errors surface as NGT::Exception carrying the C API's message.  Graph-only
+ * construction throws: it is outside this build's scope.  Object removal
+ * (Index::remove, both forms) runs on the device.  The ONNG reconstruction is NGT::GraphOptimizer
  * (NGT/GraphOptimizer.h), refine-anng is NGT::GraphReconstructor::refineANNG
  * (NGT/GraphReconstructor.h).
  */
@@ -49,6 +49,7 @@
 namespace NGT {
 
 typedef float Distance;
+typedef ::ObjectID ObjectID;  // NGT::ObjectID (lib/NGT/Common.h), the C API's type
 
 class Exception : public std::exception {
  public:
@@ -457,10 +458,23 @@ class Index {
     }
   }
 
+  // GraphAndTreeIndex::remove (Index.h:1386-1455) on the device.  `force` is
+  // accepted; its extra paths (an object gone but still in the tree or the
+  // graph) are not part of this build and it behaves as false.
   virtual void remove(ObjectID id, bool force = false) {
     (void)force;
     detail::Err err;
     if (!ngt_remove_index(handle(), id, err)) err.raise("NGT::Index::remove");
+  }
+  // Index::remove(database, objects, force) (Index.cpp:235-252): open, remove
+  // the ids in order -- one that cannot be removed is passed over -- and save.
+  static void remove(const std::string& database, std::vector<ObjectID>& objects, bool force = false) {
+    (void)force;
+    Index idx(database);
+    std::vector<uint32_t> ids(objects.begin(), objects.end());
+    detail::Err err;
+    if (!ngt_batch_remove_index(idx.handle(), ids.data(), ids.size(), nullptr, err)) err.raise("NGT::Index::remove");
+    idx.saveIndex(database);
   }
   virtual ObjectSpace& getObjectSpace() { return space; }
   // GraphIndex::getEpsilonFromExpectedAccuracy over the prf AccuracyTable

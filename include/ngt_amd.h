@@ -275,6 +275,30 @@ int ngt_amd_build_set_tree(ngt_amd_index *index, const uint32_t *leaf_parent, co
                            const void *in_pivot, const uint32_t *in_child, const float *in_border,
                            uint32_t n_internal, uint32_t root);
 
+/* ---- object removal ------------------------------------------------------- *
+ * After ngt_amd_build_begin + ngt_amd_build_set_graph + ngt_amd_build_set_tree:
+ * GraphAndTreeIndex::remove of ids[0..n) in order (lib/NGT/Index.h:1386-1455,
+ * Graph.cpp:641-864 built with NGT_FORCED_REMOVE).  graph_rows of
+ * ngt_amd_build_set_graph is the graph repository's size: a stored object
+ * below it has a node even when its list is empty.  status[i]: 0 removed, 1 no
+ * such object, 2 other failure (message via ngt_amd_last_error for the last
+ * one); a failing id leaves graph, tree and objects as they were.  An emptied
+ * leaf stays in the tree (the collapse of an all-empty subtree,
+ * Tree.cpp:338-397, is not reproduced).  The getters above return the result;
+ * the removed rows' validity flags are cleared on the index. */
+int ngt_amd_build_remove(ngt_amd_index *index, const uint32_t *ids, uint64_t n, uint8_t *status);
+/* The longest neighbour list the session's removals relinked. */
+uint64_t ngt_amd_build_longest_removed_list(const ngt_amd_index *index);
+/* The relink chain of removeEdgesReliably (Graph.cpp:739-845) over the rows of
+ * nbr_ids[0..d) in that order: link i (0 <= i < d-1) joins the id at position i
+ * of the current order with the first strict minimum among later positions;
+ * out: link_a/link_b [d-1] ids, link_dist [d-1]. */
+int ngt_amd_remove_relink(ngt_amd_index *index, const uint32_t *nbr_ids, uint32_t d,
+                          uint32_t *link_a, uint32_t *link_b, float *link_dist);
+/* Longest list whose rows the one-launch chain keeps in LDS (when they fit);
+ * longer lists (hubs) go through a d x d distance matrix in HBM. */
+uint32_t ngt_amd_remove_fast_path_capacity(void);
+
 /* ---- ONNG reconstruction -------------------------------------------------- *
  *   ngt_amd_onng_reconstruct <- the graph stages of GraphOptimizer::execute
  *   (lib/NGT/GraphOptimizer.h:230-296) on a host CSR graph (node v's list

@@ -114,6 +114,10 @@ def declare(L):
         "ngt_amd_build_set_graph": (c_int, [vp, vp, vp, vp, c_uint64]),
         "ngt_amd_build_set_tree": (c_int, [vp, vp, vp, vp, vp, vp, vp, c_uint32, vp, vp, vp, vp, c_uint32,
                                            c_uint32]),
+        "ngt_amd_build_remove": (c_int, [vp, vp, c_uint64, vp]),
+        "ngt_amd_build_longest_removed_list": (c_uint64, [vp]),
+        "ngt_amd_remove_relink": (c_int, [vp, vp, c_uint32, vp, vp, vp]),
+        "ngt_amd_remove_fast_path_capacity": (c_uint32, []),
         "ngt_amd_onng_reconstruct": (c_int, [c_int, vp, vp, vp, c_uint64, POINTER(OnngParams), u64p]),
         "ngt_amd_onng_get_graph": (c_int, [vp, vp, vp]),
         "ngt_amd_onng_last_stats": (c_int, [POINTER(OnngStats)]),
@@ -200,6 +204,7 @@ def declare(L):
         "ngt_batch_insert_index": (c_bool, [vp, f32p, c_uint32, u32p, vp]),
         "ngt_create_index": (c_bool, [vp, c_uint32, vp]),
         "ngt_remove_index": (c_bool, [vp, c_uint, vp]),
+        "ngt_batch_remove_index": (c_bool, [vp, vp, c_size_t, vp, vp]),
         "ngt_get_object_space": (vp, [vp, vp]),
         "ngt_get_object_as_float": (f32p, [vp, c_uint, vp]),
         "ngt_get_object_as_integer": (POINTER(c_uint8), [vp, c_uint, vp]),

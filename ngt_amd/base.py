@@ -238,6 +238,21 @@ class Index(object):
         return DeviceIndex.wrap(h, int(self.distance_type), "float" if self.is_float else "uint8", self.dim,
                                 nrows=int(self._L.ngt_get_object_repository_size(self.index, self.err)))
 
+    def remove(self, object_id):
+        """ngt_remove_index (python/ngt/base.py remove): the object leaves the
+        repository, the tree and the graph, whose neighbours are relinked on
+        the GPU; raises NativeError with the C API's message for a missing id."""
+        self._check(self._L.ngt_remove_index(self.index, int(object_id), self.err), self.err)
+
+    def batch_remove(self, object_ids):
+        """ngt_batch_remove_index: the ids in order in one device session;
+        returns a bool array, False where an id was passed over."""
+        ids = np.ascontiguousarray(object_ids, dtype=np.uint32)
+        done = np.zeros(len(ids), np.uint8)
+        self._check(self._L.ngt_batch_remove_index(self.index, ids.ctypes.data, len(ids), done.ctypes.data,
+                                                   self.err), self.err)
+        return done.astype(bool)
+
     def save(self, path=None):
         if path is None:
             path = self.path

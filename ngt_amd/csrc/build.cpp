@@ -34,6 +34,7 @@
 #include "../../include/ngt_amd.h"
 #include "index_internal.h"
 #include "ngt_kernels.h"
+#include "remove_kernels.h"
 
 using namespace ngt_amd;
 
@@ -442,6 +443,7 @@ extern "C" int ngt_amd_build_set_graph(ngt_amd_index* ix, const uint64_t* offset
   const uint64_t S = b.adj_stride;
   std::vector<uint32_t> adj((size_t)ix->nrows * S, 0u);
   b.graph_size = 0;
+  b.node_rows = graph_rows;
   for (uint64_t v = 0; v < graph_rows; v++) {
     const uint64_t e0 = offsets[v], e1 = offsets[v + 1];
     auto& node = b.graph[v];
@@ -502,6 +504,316 @@ extern "C" int ngt_amd_build_set_tree(ngt_amd_index* ix, const uint32_t* leaf_pa
   b.n_internal = n_internal;
   b.root = root;
   return 0;
+}
+
+// ---- object removal ---------------------------------------------------------
+// GraphAndTreeIndex::remove (lib/NGT/Index.h:1386-1455) on the session's graph
+// and tree: the duplicate search (the graph-search kernel seeded with the
+// object itself), DVPTree::remove / replace on the leaf the object descends to
+// (the tree-seed kernel's descent; the leaf row is edited on the host), and
+// NeighborhoodGraph::removeEdgesReliably (Graph.cpp:641-864, NGT_FORCED_REMOVE)
+// on the host lists with the relink chain computed by remove_kernels.hip.
+namespace {
+
+uint32_t remove_fast_cap() {
+  uint32_t cap = removal::kFastCap;
+  if (const char* v = ngt_amd::knob("NGT_AMD_REMOVE_FAST_CAP")) cap = std::min<uint32_t>(cap, (uint32_t)std::max(0, atoi(v)));
+  return cap;
+}
+
+// the relink chain over the rows of nbr[0..d) (host ids, each a stored row);
+// without `wait` the links arrive once the index's stream is synchronised
+int relink(ngt_amd_index* ix, RemoveScratch& sc, const uint32_t* nbr, uint32_t d, uint32_t* la, uint32_t* lb,
+           float* ld, bool wait) {
+  if (d < 2) return 0;
+  if (d > removal::kMaxList)
+    return fail("ngt_amd_remove_relink: a list of %u neighbours exceeds the supported %u", d, removal::kMaxList);
+  hipStream_t s = ix->stream;
+  HIP_OK(sc.ids.upload_async(nbr, d, s));
+  HIP_OK(sc.la.alloc(d - 1));
+  HIP_OK(sc.lb.alloc(d - 1));
+  HIP_OK(sc.ld.alloc(d - 1));
+  removal::RelinkArgs a{};
+  a.rows = ix->rows.p;
+  a.row_bytes = ix->row_bytes;
+  a.dp = (int)ix->dp;
+  a.ids = sc.ids.p;
+  a.d = d;
+  a.link_a = sc.la.p;
+  a.link_b = sc.lb.p;
+  a.link_dist = sc.ld.p;
+  if (removal::fast_lds_bytes(d, ix->row_bytes, remove_fast_cap())) {
+    HIP_OK(removal::launch_relink_fast(a, ix->metric, ix->otype, s));
+  } else {
+    HIP_OK(sc.matrix.alloc((size_t)d * d));
+    a.matrix = sc.matrix.p;
+    HIP_OK(removal::launch_relink_matrix(a, ix->metric, ix->otype, s));
+  }
+  HIP_OK(hipMemcpyAsync(la, sc.la.p, (d - 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  HIP_OK(hipMemcpyAsync(lb, sc.lb.p, (d - 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  HIP_OK(hipMemcpyAsync(ld, sc.ld.p, (d - 1) * sizeof(float), hipMemcpyDeviceToHost, s));
+  if (wait) HIP_OK(hipStreamSynchronize(s));
+  return 0;
+}
+
+// a graph node exists: it has edges, or it lost them all to earlier removals
+bool has_node(const ngt_amd_index* ix, const BuildState& b, uint32_t id) {
+  return b.in_graph[id] || (ix->h_valid[id] && id < b.node_rows);
+}
+
+int drop_object(ngt_amd_index* ix, uint32_t id) {
+  const uint8_t zero = 0;
+  ix->h_valid[id] = 0;
+  HIP_OK(hipMemcpy(ix->valid.p + id, &zero, 1, hipMemcpyHostToDevice));
+  ix->rows_version++;
+  return 0;
+}
+
+// 0 removed, 1 no such object, 2 refused (nothing changed), -1 device failure
+// st (nullable): seconds spent enqueueing, waiting, on the leaf, on the lists, on the adjacency
+int remove_one(ngt_amd_index* ix, BuildState& b, RemoveScratch& sc, uint32_t id, double* st) {
+  auto t_last = std::chrono::steady_clock::now();
+  auto mark = [&](int i) {
+    if (!st) return;
+    auto t = std::chrono::steady_clock::now();
+    st[i] += std::chrono::duration<double>(t - t_last).count();
+    t_last = t;
+  };
+  hipStream_t s = ix->stream;
+  const uint64_t rb = ix->row_bytes;
+  if (id == 0 || id >= ix->nrows || !ix->h_valid[id]) {
+    fail("get: Not in-memory or invalid offset of node. idx=%u size=%llu", id, (unsigned long long)ix->nrows);
+    return 1;
+  }
+  if (!has_node(ix, b, id)) return drop_object(ix, id);  // Index.h:1411-1422
+
+  // The reference's search throws when it evaluates a neighbour whose object
+  // is gone (Graph.cpp:603; a directed graph keeps edges to removed nodes),
+  // which refuses the id before anything changes: the same test on the lists
+  // the search expands -- the node's own and, below, its duplicate's.
+  auto evaluated_edges_exist = [&](uint32_t v) {
+    const auto& n = b.graph[v];
+    const size_t lim = b.edge_size_for_search <= 0 ? n.size() : std::min<size_t>(n.size(), b.edge_size_for_search);
+    for (size_t j = 0; j < lim; j++)
+      if (n[j].first >= ix->nrows || !ix->h_valid[n[j].first]) {
+        fail("get: Not in-memory or invalid offset of node. idx=%u size=%llu", n[j].first,
+             (unsigned long long)ix->nrows);
+        return false;
+      }
+    return true;
+  };
+  if (!evaluated_edges_exist(id)) return 2;
+
+  // ---- the neighbours to relink (nothing is edited before every check) -----
+  std::vector<uint32_t> nbr;
+  std::vector<float> nbr_d;
+  for (const auto& e : b.graph[id]) {
+    if (e.first == id) continue;  // a self edge is erased
+    if (e.first >= ix->nrows || !ix->h_valid[e.first] || !has_node(ix, b, e.first)) {
+      fail("removeEdgesReliably : Relink error ID=%u: neighbour %u has no object or no node", id, e.first);
+      return 2;
+    }
+    nbr.push_back(e.first);
+    nbr_d.push_back(e.second);
+  }
+  const uint32_t d = (uint32_t)nbr.size();
+  if (d > removal::kMaxList) {
+    fail("ngt_amd_build_remove: node %u has %u neighbours, more than the supported %u", id, d, removal::kMaxList);
+    return 2;
+  }
+
+  // ---- the duplicate search (Index.h:1423-1432) ---------------------------
+  const uint8_t* d_row = ix->rows.p + (uint64_t)id * rb;
+  const uint64_t soff[2] = {0, 1};
+  HIP_OK(sc.seed.upload_async(&id, 1, s));
+  HIP_OK(sc.soff.upload_async(soff, 2, s));
+  HIP_OK(sc.oi.alloc(2));
+  HIP_OK(sc.od.alloc(2));
+  HIP_OK(sc.on.alloc(1));
+  ngt_amd_search_params p{};
+  p.k = 2;
+  p.epsilon = 0.1f;
+  p.radius = 0.0f;
+  p.edge_size = -1;
+  p.seed_mode = NGT_AMD_SEED_GIVEN;
+  p.visited_hash_log2 = 0;
+  if (ngt_amd_search_device(ix, &p, d_row, rb, 1, sc.seed.p, sc.soff.p, sc.oi.p, sc.od.p, sc.on.p, nullptr, s))
+    return -1;
+  uint32_t found[2] = {0, 0}, nfound = 0;
+  HIP_OK(hipMemcpyAsync(found, sc.oi.p, sizeof found, hipMemcpyDeviceToHost, s));
+  HIP_OK(hipMemcpyAsync(&nfound, sc.on.p, sizeof nfound, hipMemcpyDeviceToHost, s));
+
+  // ---- the descent to the object's leaf (Tree.h:156-176) and the relink
+  //      chain of the neighbours, behind the search on the same stream: the
+  //      three need nothing from one another, so one wait serves them all ----
+  TreeSeedArgs t{};
+  HIP_OK(sc.tseeds.alloc(kTreeSeedStride));
+  HIP_OK(sc.tcnt.alloc(1));
+  HIP_OK(sc.pleaf.alloc(1));
+  HIP_OK(sc.pcnt.alloc(1));
+  HIP_OK(sc.pdist.alloc(1));
+  t.queries = d_row;
+  t.query_bytes = rb;
+  t.nq = 1;
+  t.dp = (int)ix->dp;
+  t.row_bytes = rb;
+  t.in_pivot = b.in_pivot.p;
+  t.in_child = b.in_child.p;
+  t.in_border = b.in_border.p;
+  t.children = 5;
+  t.root = b.root;
+  t.leaf_count = b.lf_count.p;
+  t.leaf_stride = kLeafCap;
+  t.leaf_ids = b.lf_ids.p;
+  t.seed_size = 1;
+  t.k = 1;
+  t.all_leaf_nodes = 0;
+  t.seeds = sc.tseeds.p;
+  t.seed_stride = kTreeSeedStride;
+  t.seed_count = sc.tcnt.p;
+  t.out_leaf = sc.pleaf.p;
+  t.out_count = sc.pcnt.p;
+  t.out_pdist = sc.pdist.p;
+  t.leaf_pivot = b.lf_pivot.p;
+  HIP_OK(launch_tree_seeds(t, ix->metric, ix->otype, s));
+  uint32_t leaf = 0, cnt = 0;
+  HIP_OK(hipMemcpyAsync(&leaf, sc.pleaf.p, sizeof leaf, hipMemcpyDeviceToHost, s));
+  HIP_OK(hipMemcpyAsync(&cnt, sc.pcnt.p, sizeof cnt, hipMemcpyDeviceToHost, s));
+  std::vector<uint32_t> la(d ? d - 1 : 0), lb(d ? d - 1 : 0);
+  std::vector<float> ld(d ? d - 1 : 0);
+  if (relink(ix, sc, nbr.data(), d, la.data(), lb.data(), ld.data(), false)) return -1;
+  int serr = 0;
+  mark(0);
+  if (take_device_error(ix, s, &serr)) return -1;
+  if (serr) return fail("ngt_amd_build_remove: device error flag %d in the duplicate search", serr);
+  if (nfound == 0) {
+    fail("Not found the specified id");
+    return 2;
+  }
+  const uint32_t replace_id = nfound == 1 ? 0u : (found[0] == id ? found[1] : found[0]);
+  if (replace_id != 0 && (replace_id >= ix->nrows || !evaluated_edges_exist(replace_id))) return 2;
+
+  mark(1);
+  // ---- DVPTree::remove / replace (Tree.h:178-202, Node.cpp:229-280) --------
+  if (leaf == 0 || leaf >= b.n_leaf || cnt >= kLeafCap)
+    return fail("ngt_amd_build_remove: the tree descent of %u ended at leaf %u with %u objects", id, leaf, cnt);
+  uint32_t lids[kLeafCap];
+  float ldst[kLeafCap];
+  if (cnt) {
+    HIP_OK(hipMemcpy(lids, b.lf_ids.p + (size_t)leaf * kLeafCap, cnt * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(ldst, b.lf_dist.p + (size_t)leaf * kLeafCap, cnt * sizeof(float), hipMemcpyDeviceToHost));
+  }
+  uint32_t at = 0;
+  while (at < cnt && lids[at] != id) at++;
+  if (replace_id != 0) {
+    // the duplicate takes the leaf entry; a leaf without the entry is ignored (Index.h:1448-1452)
+    if (at < cnt)
+      HIP_OK(hipMemcpy(b.lf_ids.p + (size_t)leaf * kLeafCap + at, &replace_id, sizeof(uint32_t), hipMemcpyHostToDevice));
+  } else {
+    if (at == cnt) {
+      fail("remove:: cannot remove from tree. id=%u VpTree::remove: Inner error. Cannot remove object. leafNode=%u:"
+           "VpTree::Leaf::remove: Warning. Cannot find the specified object. ID=%u,0 idx=%u If the same objects "
+           "were inserted into the index, ignore this message.", id, leaf, id, at);
+      return 2;
+    }
+    for (uint32_t j = at; j + 1 < cnt; j++) {
+      lids[j] = lids[j + 1];
+      ldst[j] = ldst[j + 1];
+    }
+    cnt--;
+    if (cnt > at) {
+      HIP_OK(hipMemcpy(b.lf_ids.p + (size_t)leaf * kLeafCap + at, lids + at, (cnt - at) * sizeof(uint32_t),
+                       hipMemcpyHostToDevice));
+      HIP_OK(hipMemcpy(b.lf_dist.p + (size_t)leaf * kLeafCap + at, ldst + at, (cnt - at) * sizeof(float),
+                       hipMemcpyHostToDevice));
+    }
+    HIP_OK(hipMemcpy(b.lf_count.p + leaf, &cnt, sizeof(uint32_t), hipMemcpyHostToDevice));
+    // an emptied leaf stays in place; the collapse of an all-empty subtree
+    // (removeEmptyNodes, Tree.cpp:338-397) is not reproduced
+  }
+
+  mark(2);
+  // ---- removeEdgesReliably on the host lists --------------------------------
+  for (uint32_t i = 0; i < d; i++) {
+    auto& n = b.graph[nbr[i]];
+    const std::pair<uint32_t, float> e{id, nbr_d[i]};
+    auto it = std::lower_bound(n.begin(), n.end(), e, od_less);
+    if (it != n.end() && it->first == id) n.erase(it);  // else "cannot find an edge ... anyway continue"
+  }
+  for (uint32_t i = 0; i + 1 < d; i++) {
+    auto link = [&](uint32_t from, uint32_t to) {
+      auto& n = b.graph[from];
+      const std::pair<uint32_t, float> e{to, ld[i]};
+      auto it = std::lower_bound(n.begin(), n.end(), e, od_less);
+      if (it == n.end() || it->first != to) n.insert(it, e);
+    };
+    link(la[i], lb[i]);
+    link(lb[i], la[i]);
+  }
+  b.graph[id].clear();
+  b.in_graph[id] = 0;
+
+  mark(3);
+  // ---- the padded adjacency of the touched nodes, the object ----------------
+  std::vector<uint32_t> dirty(nbr);
+  dirty.push_back(id);
+  std::sort(dirty.begin(), dirty.end());
+  dirty.erase(std::unique(dirty.begin(), dirty.end()), dirty.end());
+  std::vector<uint32_t> vals(dirty.size() * b.adj_stride, 0u);
+  for (size_t i = 0; i < dirty.size(); i++) {
+    const auto& node = b.graph[dirty[i]];
+    const size_t m = std::min<size_t>(node.size(), b.adj_stride);
+    for (size_t j = 0; j < m; j++) vals[i * b.adj_stride + j] = node[j].first;
+  }
+  HIP_OK(sc.dirty.upload_async(dirty.data(), dirty.size(), s));
+  HIP_OK(sc.vals.upload_async(vals.data(), vals.size(), s));
+  HIP_OK(launch_adj_scatter(ix->adj.p, b.adj_stride, sc.dirty.p, sc.vals.p, (uint32_t)dirty.size(), s));
+  HIP_OK(hipStreamSynchronize(s));
+  ix->adj_version++;
+  b.longest_removed_list = std::max<uint64_t>(b.longest_removed_list, d);
+  mark(4);
+  return drop_object(ix, id);
+}
+
+}  // namespace
+
+extern "C" uint32_t ngt_amd_remove_fast_path_capacity(void) { return removal::kFastCap; }
+
+extern "C" int ngt_amd_remove_relink(ngt_amd_index* ix, const uint32_t* nbr_ids, uint32_t d, uint32_t* link_a,
+                                     uint32_t* link_b, float* link_dist) {
+  if (!ix || (d && !nbr_ids) || (d > 1 && (!link_a || !link_b || !link_dist)))
+    return fail("ngt_amd_remove_relink: bad arguments");
+  if (ix->nrows == 0 || !ix->rows.p) return fail("ngt_amd_remove_relink: set the objects first");
+  for (uint32_t i = 0; i < d; i++)
+    if (nbr_ids[i] == 0 || nbr_ids[i] >= ix->nrows)
+      return fail("ngt_amd_remove_relink: id %u out of range", nbr_ids[i]);
+  HIP_OK(hipSetDevice(ix->device));
+  RemoveScratch sc;
+  return relink(ix, sc, nbr_ids, d, link_a, link_b, link_dist, true);
+}
+
+extern "C" int ngt_amd_build_remove(ngt_amd_index* ix, const uint32_t* ids, uint64_t n, uint8_t* status) {
+  if (!ix || !ix->build || (n && (!ids || !status))) return fail("ngt_amd_build_remove: bad arguments");
+  HIP_OK(hipSetDevice(ix->device));
+  ServeHold serve_hold(ix);
+  BuildState& b = *ix->build;
+  RemoveScratch& sc = b.remove_scratch;  // no allocation per id once warm
+  // NGT_AMD_BUILD_PROFILE=1: per-stage wall time on stderr
+  const bool prof = ngt_amd::knob("NGT_AMD_BUILD_PROFILE") != nullptr;
+  double st[5] = {0, 0, 0, 0, 0};
+  for (uint64_t i = 0; i < n; i++) {
+    const int r = remove_one(ix, b, sc, ids[i], prof ? st : nullptr);
+    if (r < 0) return -1;
+    status[i] = (uint8_t)r;
+  }
+  if (prof)
+    fprintf(stderr, "build_remove %llu ids: enqueue %.3f s, wait %.3f s, leaf %.3f s, lists %.3f s, adjacency and "
+            "flag %.3f s\n", (unsigned long long)n, st[0], st[1], st[2], st[3], st[4]);
+  return 0;
+}
+
+extern "C" uint64_t ngt_amd_build_longest_removed_list(const ngt_amd_index* ix) {
+  return ix && ix->build ? ix->build->longest_removed_list : 0;
 }
 
 extern "C" int ngt_amd_build_graph_size(const ngt_amd_index* ix, uint64_t* graph_size, uint64_t* nedges) {

@@ -274,6 +274,68 @@ std::string append_object(CapiIndex* ix, const T* obj, uint32_t dim, uint32_t& i
   return "";
 }
 
+// The session's graph (CSR + distances) and DVP tree into the host mirror.
+// after_build: a construction's result (every node is new: prevsize and the
+// slot flags are reset); otherwise a removal's, which keeps prevsize, the
+// slot flags, the pivots' presence and the root.
+std::string fetch_session(CapiIndex* ix, bool after_build) {
+  HostIndex& h = ix->host;
+  uint64_t gsize = 0, ne = 0;
+  if (ngt_amd_build_graph_size(ix->dev, &gsize, &ne)) return amd_err();
+  std::vector<uint64_t> off(gsize + 1);
+  h.edges.resize(ne);
+  h.edge_dists.resize(ne);
+  if (ngt_amd_build_get_graph(ix->dev, off.data(), h.edges.data(), h.edge_dists.data())) return amd_err();
+  h.edge_off.assign(h.nrows + 1, ne);
+  for (uint64_t v = 0; v <= h.nrows && v <= gsize; v++) h.edge_off[v] = off[v];
+  if (after_build) h.prevsize.assign(h.nrows, 0);
+  uint32_t nl = 0, ni = 0;
+  uint64_t nli = 0;
+  if (ngt_amd_build_tree_size(ix->dev, &nl, &ni, &nli)) return amd_err();
+  ngt_amd::HostTree& t = h.tree;
+  const ngt_amd::HostTree before = after_build ? ngt_amd::HostTree() : t;
+  t = ngt_amd::HostTree();
+  t.leaf_parent.resize(nl);
+  t.leaf_off.resize((size_t)nl + 1);
+  t.leaf_ids.resize(nli);
+  t.leaf_dists.resize(nli);
+  t.leaf_has_pivot.resize(nl);
+  t.leaf_pivot.resize((size_t)nl * h.row_bytes);
+  t.in_parent.resize(ni);
+  t.in_pivot.resize((size_t)ni * h.row_bytes);
+  t.in_child.resize((size_t)ni * 5);
+  t.in_border.resize((size_t)ni * 4);
+  if (ngt_amd_build_get_tree(ix->dev, t.leaf_parent.data(), t.leaf_off.data(), t.leaf_ids.data(),
+                             t.leaf_dists.data(), t.leaf_has_pivot.data(), t.leaf_pivot.data(), t.in_parent.data(),
+                             t.in_pivot.data(), t.in_child.data(), t.in_border.data()))
+    return amd_err();
+  if (!after_build) {
+    if (before.leaf_valid.size() != nl || before.in_valid.size() != (ni > 1 ? ni : before.in_valid.size()))
+      return "the tree changed its node count during a removal";
+    t.leaf_valid = before.leaf_valid;
+    t.in_valid = before.in_valid;
+    t.leaf_has_pivot = before.leaf_has_pivot;
+    if (before.in_valid.size() != ni) {  // a root leaf: the session counts the dummy internal slot
+      t.in_parent = before.in_parent;
+      t.in_pivot = before.in_pivot;
+      t.in_child = before.in_child;
+      t.in_border = before.in_border;
+    }
+    t.root = before.root;
+    t.present = before.present;
+    return "";
+  }
+  t.leaf_valid.assign(nl, 1);
+  t.leaf_valid[0] = 0;
+  t.in_valid.assign(ni, 1);
+  if (ni) t.in_valid[0] = 0;
+  for (uint32_t i = 1; i < nl; i++)  // LeafNode::serialize writes the pivot unless the leaf is an empty root
+    t.leaf_has_pivot[i] = !((t.leaf_parent[i] & 0x7fffffffu) == 0 && t.leaf_off[i + 1] == t.leaf_off[i]);
+  t.root = ni > 1 ? 1u : 0x80000001u;
+  t.present = nl > 1;
+  return "";
+}
+
 // GraphAndTreeIndex::createIndex for the objects appended since the last
 // build: ANNG with the tree, on the device; the host mirror receives the
 // graph (CSR + distances) and the DVP tree for ngt_save_index and searches.
@@ -311,43 +373,79 @@ std::string build_anng(CapiIndex* ix) {
       return amd_err();
   }
   if (ngt_amd_build_insert(ix->dev, 1, h.nrows)) return amd_err();
-  uint64_t gsize = 0, ne = 0;
-  if (ngt_amd_build_graph_size(ix->dev, &gsize, &ne)) return amd_err();
-  std::vector<uint64_t> off(gsize + 1);
-  h.edges.resize(ne);
-  h.edge_dists.resize(ne);
-  if (ngt_amd_build_get_graph(ix->dev, off.data(), h.edges.data(), h.edge_dists.data())) return amd_err();
-  h.edge_off.assign(h.nrows + 1, ne);
-  for (uint64_t v = 0; v <= h.nrows && v <= gsize; v++) h.edge_off[v] = off[v];
-  h.prevsize.assign(h.nrows, 0);
-  uint32_t nl = 0, ni = 0;
-  uint64_t nli = 0;
-  if (ngt_amd_build_tree_size(ix->dev, &nl, &ni, &nli)) return amd_err();
-  ngt_amd::HostTree& t = h.tree;
-  t = ngt_amd::HostTree();
-  t.leaf_parent.resize(nl);
-  t.leaf_off.resize((size_t)nl + 1);
-  t.leaf_ids.resize(nli);
-  t.leaf_dists.resize(nli);
-  t.leaf_has_pivot.resize(nl);
-  t.leaf_pivot.resize((size_t)nl * h.row_bytes);
-  t.in_parent.resize(ni);
-  t.in_pivot.resize((size_t)ni * h.row_bytes);
-  t.in_child.resize((size_t)ni * 5);
-  t.in_border.resize((size_t)ni * 4);
-  if (ngt_amd_build_get_tree(ix->dev, t.leaf_parent.data(), t.leaf_off.data(), t.leaf_ids.data(),
-                             t.leaf_dists.data(), t.leaf_has_pivot.data(), t.leaf_pivot.data(), t.in_parent.data(),
-                             t.in_pivot.data(), t.in_child.data(), t.in_border.data()))
-    return amd_err();
-  t.leaf_valid.assign(nl, 1);
-  t.leaf_valid[0] = 0;
-  t.in_valid.assign(ni, 1);
-  if (ni) t.in_valid[0] = 0;
-  for (uint32_t i = 1; i < nl; i++)  // LeafNode::serialize writes the pivot unless the leaf is an empty root
-    t.leaf_has_pivot[i] = !((t.leaf_parent[i] & 0x7fffffffu) == 0 && t.leaf_off[i + 1] == t.leaf_off[i]);
-  t.root = ni > 1 ? 1u : 0x80000001u;
-  t.present = nl > 1;
+  e = fetch_session(ix, true);
+  if (!e.empty()) return e;
   ix->device_stale = true;
+  return "";
+}
+
+// GraphAndTreeIndex::remove of ids[0..n) in order, in one construction session
+// on the device (ngt_amd_build_remove): the host mirror keeps its rows and
+// prevsize, loses the objects' validity, and receives the edited graph and
+// tree.  status[i]: 0 removed, 1 no such object, 2 refused; `last` = the
+// message of the last id that was not removed.
+std::string remove_objects(CapiIndex* ix, const uint32_t* ids, size_t n, std::vector<uint8_t>& status,
+                           std::string& last) {
+  std::unique_lock<std::shared_mutex> wl(ix->rw);
+  HostIndex& h = ix->host;
+  status.assign(n, 1);
+  if (n == 0) return "";
+  uint64_t nodes = 0;  // the graph repository's size
+  for (uint64_t v = 0; v < h.nrows && v + 1 < h.edge_off.size(); v++)
+    if (h.edge_off[v + 1] != h.edge_off[v]) nodes = v + 1;
+  if (!h.prevsize.empty()) nodes = std::max<uint64_t>(nodes, std::min<uint64_t>(h.prevsize.size(), h.nrows));
+  bool stored = false;
+  for (size_t i = 0; i < n && !stored; i++) stored = ids[i] != 0 && ids[i] < h.nrows && h.valid[ids[i]];
+  if (nodes == 0 || !stored) {
+    // nothing is indexed yet, or no id names an object: only objects go
+    // (Index.h:1411-1422) and no session is needed
+    for (size_t i = 0; i < n; i++) {
+      if (ids[i] == 0 || ids[i] >= h.nrows || !h.valid[ids[i]]) {
+        std::stringstream ss;
+        ss << "get: Not in-memory or invalid offset of node. idx=" << ids[i] << " size=" << h.nrows;
+        last = ss.str();
+        continue;
+      }
+      h.valid[ids[i]] = 0;
+      status[i] = 0;
+      ix->device_stale = true;
+    }
+    return "";
+  }
+  if (h.prop.index_type != 0) return "object removal supports GraphAndTree indexes only";
+  if (!h.tree.present) return "the index has a graph but no DVP tree";
+  if (h.edge_off.size() < h.nrows + 1 || h.edge_dists.size() != h.edges.size())
+    return "graph arrays inconsistent with the repository";
+  std::string e = rebuild_device(ix);
+  if (!e.empty()) return e;
+  ngt_amd_build_params p{};
+  p.edge_size_for_creation = std::max(1, h.prop.edge_size_for_creation);
+  p.edge_size_for_search = h.prop.edge_size_for_search;
+  p.batch_size_for_creation = std::max(1, h.prop.batch_size_for_creation);
+  p.seed_size = h.prop.seed_size;
+  p.epsilon_for_creation = (float)h.prop.epsilon_for_creation;
+  const ngt_amd::HostTree& t = h.tree;
+  const uint32_t nl = (uint32_t)t.leaf_parent.size(), ni = (uint32_t)t.in_parent.size();
+  // from here on the device copy serves the session, whatever the outcome
+  ix->device_stale = true;
+  if (ngt_amd_build_begin(ix->dev, &p) ||
+      ngt_amd_build_set_graph(ix->dev, h.edge_off.data(), h.edges.data(), h.edge_dists.data(), nodes) ||
+      ngt_amd_build_set_tree(ix->dev, t.leaf_parent.data(), t.leaf_off.data(), t.leaf_ids.data(),
+                             t.leaf_dists.data(), t.leaf_has_pivot.data(), t.leaf_pivot.data(), nl,
+                             t.in_parent.data(), t.in_pivot.data(), t.in_child.data(), t.in_border.data(),
+                             ni < 1 ? 1u : ni, t.root))
+    return amd_err();
+  if (ngt_amd_build_remove(ix->dev, ids, n, status.data())) return amd_err();
+  bool any = false;
+  for (size_t i = 0; i < n; i++) {
+    if (status[i] != 0) last = amd_err();  // the session keeps the last refusal's message
+    else any = true;
+  }
+  if (!any) return "";
+  e = fetch_session(ix, false);
+  if (!e.empty()) return e;
+  for (size_t i = 0; i < n; i++)
+    if (status[i] == 0) h.valid[ids[i]] = 0;
   return "";
 }
 
@@ -853,13 +951,42 @@ bool ngt_create_index(NGTIndex index, uint32_t pool_size, NGTError error) {
   return true;
 }
 bool ngt_remove_index(NGTIndex index, ObjectID id, NGTError error) {
-  (void)id;
   if (index == NULL) {
     param_error(error, __FUNCTION__, "index = 0");
     return false;
   }
-  set_error(error, __FUNCTION__, kNotImplemented);
-  return false;
+  std::vector<uint8_t> status;
+  std::string last;
+  const uint32_t one = id;
+  std::string e = remove_objects(static_cast<CapiIndex*>(index), &one, 1, status, last);
+  if (e.empty() && status[0] != 0) e = last;
+  if (!e.empty()) {
+    set_error(error, __FUNCTION__, e);
+    return false;
+  }
+  return true;
+}
+// NGT::Index::remove(database, ids) (Index.cpp:235-252) without the open and
+// the save: one session for the list; a refused id is marked and passed over.
+bool ngt_batch_remove_index(NGTIndex index, const uint32_t* ids, size_t n, uint8_t* removed, NGTError error) {
+  if (index == NULL) {
+    param_error(error, __FUNCTION__, "index = 0");
+    return false;
+  }
+  if (ids == NULL && n != 0) {
+    param_error(error, __FUNCTION__, "ids = 0");
+    return false;
+  }
+  std::vector<uint8_t> status;
+  std::string last;
+  std::string e = remove_objects(static_cast<CapiIndex*>(index), ids, n, status, last);
+  if (!e.empty()) {
+    set_error(error, __FUNCTION__, e);
+    return false;
+  }
+  if (removed)
+    for (size_t i = 0; i < n; i++) removed[i] = status[i] == 0;
+  return true;
 }
 
 NGTObjectSpace ngt_get_object_space(NGTIndex index, NGTError error) {
@@ -1264,6 +1391,12 @@ bool ngt_get_edges(NGTIndex index, ObjectID id, NGTObjectDistances edges, NGTErr
   HostIndex& h = static_cast<CapiIndex*>(index)->host;
   if (id == 0 || id >= h.nrows) {
     set_error(error, __FUNCTION__, "the specified ID is out of the range");
+    return false;
+  }
+  if (!h.valid[id] && h.edge_off[id] == h.edge_off[id + 1]) {  // an empty graph slot (GraphRepository::get)
+    std::stringstream ss;
+    ss << "get: Not in-memory or invalid offset of node. idx=" << id << " size=" << h.nrows;
+    set_error(error, __FUNCTION__, ss.str());
     return false;
   }
   Results* r = static_cast<Results*>(edges);

@@ -189,6 +189,13 @@ struct GlibcRandHost {
 // the padded search adjacency the insertion searches read (HBM).
 struct Server;  // serve.cpp
 
+// device scratch of object removal (build.cpp), kept for the session
+struct RemoveScratch {
+  DevBuf<uint32_t> ids, la, lb, seed, oi, on, tseeds, tcnt, pleaf, pcnt, dirty, vals;
+  DevBuf<uint64_t> soff;
+  DevBuf<float> ld, od, pdist, matrix;
+};
+
 struct BuildState {
   int32_t edge_size_for_creation = 10, edge_size_for_search = 40, batch_size = 200, seed_size = 10;
   float epsilon_for_creation = 0.1f;
@@ -204,6 +211,12 @@ struct BuildState {
   uint32_t root = 0x80000001u;
   GlibcRandHost rnd;
   uint64_t adj_stride = 0;
+  // removal (ngt_amd_build_remove): the graph repository slots loaded by
+  // ngt_amd_build_set_graph -- a valid object below it has a node even with
+  // no edges left -- and the longest neighbour list a removal relinked
+  uint64_t node_rows = 0;
+  uint64_t longest_removed_list = 0;
+  RemoveScratch remove_scratch;
 };
 
 }  // namespace ngt_amd

@@ -260,6 +260,22 @@ class DeviceIndex(object):
         t["root"] = 1 if ni > 1 else 0x80000001
         return t
 
+    # ---- object removal (GraphAndTreeIndex::remove) ---------------------------
+    def remove_relink(self, nbr_ids):
+        """The relink chain of removeEdgesReliably over the rows of nbr_ids in
+        that order: (link_a, link_b, link_dist), one link per position but the last."""
+        ids = np.ascontiguousarray(nbr_ids, dtype=np.uint32)
+        m = max(len(ids) - 1, 0)
+        la, lb, ld = np.zeros(max(m, 1), np.uint32), np.zeros(max(m, 1), np.uint32), np.zeros(max(m, 1), np.float32)
+        _chk(self.L.ngt_amd_remove_relink(self.h, ids.ctypes.data, len(ids), la.ctypes.data, lb.ctypes.data,
+                                          ld.ctypes.data))
+        return la[:m], lb[:m], ld[:m]
+
+    @staticmethod
+    def remove_fast_path_capacity():
+        """Longest neighbour list the one-launch relink chain takes."""
+        return int(lib().ngt_amd_remove_fast_path_capacity())
+
     # ---- NGTQG quantized graph (L2 float) ---------------------------------
     def qg_set_quantizer(self, global_centroid, local):
         """global_centroid: [dim]; local: [M, 16, dsub] (local ids 1..16)."""

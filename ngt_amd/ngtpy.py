@@ -177,11 +177,11 @@ class Index(object):
         return [float(x) for x in self._ix.get_object(self._id_in(object_id))]
 
     def remove(self, object_id):
-        """Not supported: GraphAndTreeIndex::remove re-links the graph around the
-        removed node (graph maintenance, out of this build's scope); raises
+        """ngtpy.cpp remove -> GraphAndTreeIndex::remove: the object leaves the
+        repository, the tree and the graph, and its neighbours are relinked, on
+        the GPU.  The id follows zero_based_numbering; a missing id raises
         NativeError with the C API's message."""
-        L = self._ix._L
-        self._ix._check(L.ngt_remove_index(self._ix.index, self._id_in(object_id), self._ix.err), self._ix.err)
+        self._ix.remove(self._id_in(object_id))
 
     def refine_anng(self, epsilon=0.1, expected_accuracy=0.0, num_of_edges=0, num_of_explored_edges=INT_MIN,
                     batch_size=10000):
