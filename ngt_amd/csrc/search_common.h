@@ -515,10 +515,11 @@ __device__ __forceinline__ uint32_t filter_threshold(float expr, double fe, doub
 //   q.x  <= q.x~ + |q| E,   |x| >= |x~| - E,
 //   q.x~ =  a sum q + b (a sum c + b sum q''c + r.c),  r.c <= |r| |c|,
 //   |x~|^2 = Dp a^2 + 2ab sum c + b^2 sum c^2,
-// so cos(q, x) <= U = (q.x~ + |q| E) / (|q| (|x~| - E)) (1 when |x~| <= E).
+// so cos(q, x) <= U = (q.x~ + |q| E) / (|q| (|x~| - E)) (no bound when |x~| <= E).
 // The comparator's float sums (PrimitiveComparator.h:487-553: 16 lanes of
 // Dp/16 FMAs and a 16->1 fold) sit within 8e-6 of the real cosine; with 2e-5
-// of slack the distance is at least 1 - (U + 2e-5) (cosine) or
+// of slack the distance is at least 1 - (U + 2e-5) (cosine: below 0 when
+// U + 2e-5 > 1, as the comparator's own 1 - cs can be; -inf when |x~| <= E) or
 // acos(min(1, U + 2e-5)) (angle), stored rounded down.  sum c, sum c^2 and
 // sum q''c are exact u32 sums of v_dot4_u32_u8; 16 lanes per row, dword d of
 // a row on lane d mod 16 (64 contiguous bytes per row per load instruction),
@@ -563,14 +564,28 @@ __device__ __forceinline__ float cos_filter_bound(uint32_t sc, uint32_t scc, uin
   const double x2 = (double)dp * a * a + 2.0 * a * b * (double)sc + b * b * (double)scc;
   const double xn = sqrt(x2 > 0.0 ? x2 : 0.0);
   double u = 1.0;
+  bool known = false;
   if (xn > e * (1.0 + 1e-9) && fq.qn > 0.0) {
     const double num = qx * (1.0 + 1e-12) + fabs(qx) * 1e-12 + fq.qn * e;
     u = num >= 0.0 ? num / (fq.qn * (xn - e) * (1.0 - 1e-12)) : num / (fq.qn * (xn + e) * (1.0 + 1e-12));
     u += 2e-5;
+    known = u == u;
   }
+  if constexpr (M == kCosine) {
+    // The comparator's 1 - cs is negative when its float cosine rounds above
+    // 1 (near-parallel rows: a narrow cluster far from the origin), and so is
+    // the exploration radius once k such results are in: the bound follows u
+    // past 1 instead of stopping at distance 0, and without a bound nothing
+    // is rejected.
+    if (!known) return -__builtin_huge_valf();
+    if (u < -1.0) u = -1.0;
+    const double lb = 1.0 - u;
+    return __double2float_rd(lb >= 0.0 ? lb * (1.0 - 1e-12) : lb * (1.0 + 1e-12));
+  }
+  // angle_of clamps the cosine to [-1, 1]: the angle is never below 0
   if (!(u < 1.0)) u = 1.0;  // NaN included
   if (u < -1.0) u = -1.0;
-  const double lb = M == kCosine ? 1.0 - u : acos(u);
+  const double lb = acos(u);
   return __double2float_rd(lb * (1.0 - 1e-12));
 }
 

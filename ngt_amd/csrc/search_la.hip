@@ -268,7 +268,7 @@ ngt_graph_search_la_kernel(SearchArgs a) {
       }
       lo = (uint32_t)(wave_min_u64(lo) & 0xffffffffu);
       hi = (uint32_t)(~wave_min_u64(~(uint64_t)hi) & 0xffffffffu);
-      uint32_t bound = 0;  // spill keys with ord < bound move to LDS
+      uint64_t bound = 0;  // spill keys below bound move to LDS
       if (lo > hi) {
         nspill = 0;  // nothing within the radius: the search ends
         T = ~0ull;
@@ -296,14 +296,23 @@ ngt_graph_search_la_kernel(SearchArgs a) {
         }
         const uint64_t okm = ballot64(incl <= want);
         const uint32_t b = (uint32_t)__popcll(okm);  // bins [0, b) fit (prefix is monotone)
-        if (b >= 1 || width == 1) {
-          bound = b >= 1 ? (uint32_t)std::min<uint64_t>((uint64_t)lo + b * width, 0xffffffffull) : lo + 1;
-          if (b == 0 && lane == 0) atomicOr(a.error, 8);  // > want keys share one distance: never expected
+        if (b >= 1) {
+          bound = std::min<uint64_t>((uint64_t)lo + b * width, 0xffffffffull) << 32;
+          break;
+        }
+        if (width == 1) {
+          // more than `want` keys share the smallest distance (lattice data:
+          // few distinct distances): split them by id, on the whole keys
+          bound = lat_select(spill, nspill, want, ((uint64_t)lo << 32) | 0xffffffffull, hist);
+          if (bound == 0ull) {
+            if (lane == 0) atomicOr(a.error, 8);  // selection check: never expected
+            bound = std::min<uint64_t>((uint64_t)lo + 1, 0xffffffffull) << 32;
+          }
           break;
         }
         hi = (uint32_t)(lo + width - 1);  // the first bin alone is too big: refine it
       }
-      // move: ord < bound (and within the radius) to LDS; keep ord >= bound
+      // move: keys below bound (and within the radius) to LDS; keep the others
       // (within the radius) in the spill, compacted in place
       uint32_t out = 0;
       for (uint32_t b0 = 0; b0 < nspill; b0 += 64) {
@@ -311,10 +320,10 @@ ngt_graph_search_la_kernel(SearchArgs a) {
         const uint64_t key = i < nspill ? spill[i] : ~0ull;
         const uint32_t o = (uint32_t)(key >> 32);
         const bool in = i < nspill && o <= lim;
-        // (the histogram bounds the moved keys by want <= cq_cap / 2; the
-        // flagged degenerate bound above keeps any excess in the spill)
-        const bool fits = ncq + mbcnt(ballot64(in && o < bound)) < a.cq_cap;
-        const bool mv = in && o < bound && fits;
+        // (the selection bounds the moved keys by want <= cq_cap / 2; after
+        // the flagged failure above any excess stays in the spill)
+        const bool fits = ncq + mbcnt(ballot64(in && key < bound)) < a.cq_cap;
+        const bool mv = in && key < bound && fits;
         const bool stay = in && !mv;
         const uint64_t mm = ballot64(mv), sm = ballot64(stay);
         __builtin_amdgcn_wave_barrier();
@@ -325,7 +334,7 @@ ngt_graph_search_la_kernel(SearchArgs a) {
         out += (uint32_t)__popcll(sm);
       }
       nspill = out;
-      T = nspill ? ((uint64_t)bound << 32) : ~0ull;
+      T = nspill ? bound : ~0ull;
       __builtin_amdgcn_wave_barrier();
     };
     auto tail_insert = [&](uint64_t key) {
