@@ -11,13 +11,17 @@
  *                          keeps the old value)
  *   setProcessingModes     :628-634
  *   execute                :230-300
+ *   optimizeSearchParameters :302-384
  *
- * The three timing-driven steps (searchParameterOptimization,
- * prefetchParameterOptimization, accuracyTableGeneration) are not implemented
- * by this build; they default to true as in the reference, and execute()
- * throws while one of them is on -- switch them off as `ngt reconstruct-graph
- * -s n` does.  adjustSearchCoefficients and optimizeNumberOfEdgesForANNG are
- * outside this build's scope.
+ * Of the three tuning steps, searchParameterOptimization and
+ * prefetchParameterOptimization minimise measured query time and are not
+ * implemented by this build.  All three default to true as in the reference,
+ * and execute() throws while one of them is on -- switch them off as `ngt
+ * reconstruct-graph -s n` does.  optimizeSearchParameters(path) with
+ * accuracyTableGeneration alone (`ngt optimize-search-parameters -m a`)
+ * generates the accuracy table on the GPU and rewrites path/prf; it throws
+ * while one of the other two is on.  adjustSearchCoefficients and
+ * optimizeNumberOfEdgesForANNG are outside this build's scope.
  */
 #ifndef NGT_AMD_CXX_GRAPH_OPTIMIZER_H
 #define NGT_AMD_CXX_GRAPH_OPTIMIZER_H
@@ -85,6 +89,19 @@ class GraphOptimizer {
     searchParameterOptimization = searchParameter;
     prefetchParameterOptimization = prefetchParameter;
     accuracyTableGeneration = accuracyTable;
+  }
+
+  void optimizeSearchParameters(const std::string outIndexPath) {
+    detail::Err err;
+    NGTOptimizer opt = ngt_create_optimizer(logDisabled, err);
+    if (opt == NULL) err.raise("GraphOptimizer::optimizeSearchParameters");
+    bool ok = ngt_optimizer_set_minimum(opt, (int)numOfOutgoingEdges, (int)numOfIncomingEdges, (int)numOfQueries,
+                                        (int)numOfResults, err) &&
+              ngt_optimizer_set_processing_modes(opt, searchParameterOptimization, prefetchParameterOptimization,
+                                                 accuracyTableGeneration, err) &&
+              ngt_optimizer_optimize_search_parameters(opt, outIndexPath.c_str(), err);
+    ngt_destroy_optimizer(opt);
+    if (!ok) err.raise("GraphOptimizer::optimizeSearchParameters");
   }
 
   void execute(const std::string inIndexPath, const std::string outIndexPath) {

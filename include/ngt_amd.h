@@ -398,6 +398,31 @@ int ngt_amd_refine_last_stats(ngt_amd_refine_stats *stats);
  * global memory.  The other list kernels have no such limit. */
 uint32_t ngt_amd_refine_fast_path_capacity(void);
 
+/* ---- accuracy table ------------------------------------------------------- *
+ *   ngt_amd_accuracy_table <- Optimizer::generateAccuracyTable
+ *   (lib/NGT/Optimizer.h:1495-1573), what `ngt optimize-search-parameters -m a`
+ *   and GraphOptimizer::optimizeSearchParameters run: nqueries queries, each the
+ *   mean of two stored objects (:1139-1199); maxEpsilon, the first epsilon from
+ *   which nresults results stop changing (:1425-1481); a pseudo ground truth at
+ *   that epsilon over all edges; then a sweep of epsilon from -0.6 upward whose
+ *   mean accuracy over 20 results per query is the table (:1514-1570).  Every
+ *   batch is one ngt_amd_search with tree seeds, so the index needs rows, a
+ *   graph, a tree and its search property, and EdgeSizeForSearch 0 or -2 (the
+ *   reference's refusal otherwise, decided before any device work, as is
+ *   nresults < 20).  The table equals the reference's entry for entry.  One
+ *   deliberate difference: the reference also ends the maxEpsilon loop when
+ *   the last query's wall time exceeds 40 x its time at epsilon 0 (:1461);
+ *   here that test is made on the query's distance computations (counter [0]).
+ *   Limits: nresults and nqueries may not exceed the repository size, and a
+ *   batch is an ordinary search -- on a large index whose sweep has to go to
+ *   an epsilon at which a search overflows its unchecked-set spill (1M x 128
+ *   uniform rows over all edges: about 0.2) the call ends with that search's
+ *   "result list truncated" error instead of a table.
+ *   eps_out/acc_out hold *n entries on entry; *n is the table's size on return
+ *   (an error when it does not fit); max_epsilon is nullable. */
+int ngt_amd_accuracy_table(ngt_amd_index *index, uint64_t nresults, uint64_t nqueries, float *eps_out,
+                           double *acc_out, uint32_t *n, float *max_epsilon);
+
 /* ---- repository sharding (one shard per GPU) ------------ *
  * Merge of per-shard result lists gathered from every rank (RCCL all-gather
  * over xGMI): the k best (distance, global id) per query, the ordering of

@@ -122,6 +122,8 @@ def declare(L):
         "ngt_amd_onng_get_graph": (c_int, [vp, vp, vp]),
         "ngt_amd_onng_last_stats": (c_int, [POINTER(OnngStats)]),
         "ngt_amd_onng_fast_path_capacity": (c_uint32, []),
+        "ngt_amd_accuracy_table": (c_int, [vp, c_uint64, c_uint64, POINTER(c_float), POINTER(c_double),
+                                           POINTER(c_uint32), POINTER(c_float)]),
         "ngt_amd_refine_anng": (c_int, [vp, vp, vp, vp, c_uint64, POINTER(RefineParams), u64p]),
         "ngt_amd_refine_merge": (c_int, [c_int, vp, vp, vp, c_uint64, c_uint32, c_uint32, c_uint32, vp, vp, vp,
                                          c_int, u64p]),
@@ -229,6 +231,8 @@ def declare(L):
         "ngt_destroy_optimizer": (None, [vp]),
         "ngt_optimizer_set_shortcut_reduction": (c_bool, [vp, c_bool, c_size_t, vp]),
         "ngt_optimizer_get": (c_bool, [vp, POINTER(c_double), vp]),
+        "ngt_optimizer_optimize_search_parameters": (c_bool, [vp, c_char_p, vp]),
+        "ngt_generate_accuracy_table": (c_bool, [vp, c_size_t, c_size_t, vp]),
         "ngt_refine_anng": (c_bool, [vp, c_float, c_float, c_int, c_int, c_size_t, vp]),
         "ngt_get_edges": (c_bool, [vp, c_uint, vp, vp]),
         "ngt_get_object_repository_size": (c_uint32, [vp, vp]),

@@ -23,6 +23,7 @@
 
 #include "../../include/NGT/Capi.h"
 #include "../../include/ngt_amd.h"
+#include "accuracy_table.h"
 #include "coalesce.h"
 #include "index_io.h"
 
@@ -1056,10 +1057,11 @@ void ngt_destroy_error_object(NGTError error) { delete static_cast<std::string*>
 
 // ---- GraphOptimizer (lib/NGT/GraphOptimizer.h) -------------------------------
 // The parameters and their setters are the reference's; execute runs the graph
-// stages (edge and path adjustment) on the device (onng.cpp).  The three
-// timing-driven steps -- search-parameter optimisation, prefetch tuning,
-// accuracy-table generation -- are not reproducible and not implemented:
-// execute refuses to run while one of them is switched on.
+// stages (edge and path adjustment) on the device (onng.cpp) and refuses to
+// run while one of the three tuning steps is switched on.  Of those,
+// search-parameter optimisation and prefetch tuning minimise measured query
+// time and are not implemented; accuracy-table generation is
+// ngt_optimizer_optimize_search_parameters (further down).
 extern "C++" {
 namespace {
 
@@ -1376,6 +1378,106 @@ bool ngt_refine_anng(NGTIndex index, float epsilon, float accuracy, int noOfEdge
       set_error(error, __FUNCTION__, e);
       return false;
     }
+  } catch (std::exception& err) {
+    set_error(error, __FUNCTION__, err.what());
+    return false;
+  }
+  return true;
+}
+
+// ---- accuracy table (Optimizer::generateAccuracyTable, Optimizer.h:1495-1573)
+extern "C++" {
+namespace {
+
+// The table string of the handle's index.  The refusals come before the
+// device copy is built; the searches hold `rw` shared.
+std::string accuracy_table_of(CapiIndex* ix, size_t nresults, size_t nqueries, std::string& table) {
+  {
+    std::shared_lock<std::shared_mutex> rd(ix->rw);
+    std::string e = ngt_amd::accuracy_refusal(ix->host.prop.edge_size_for_search, nresults);
+    if (!e.empty()) return e;
+    if (!use_tree(ix))
+      return "Optimizer::generateAccuracyTable: the MI355X build takes GraphAndTree indexes only (the searches take "
+             "tree seeds)";
+  }
+  std::shared_lock<std::shared_mutex> rd;
+  std::string e = sync_device(ix, rd);
+  if (!e.empty()) return e;
+  std::vector<float> eps(256);
+  std::vector<double> acc(256);
+  uint32_t n = (uint32_t)eps.size();
+  int rc = ngt_amd_accuracy_table(ix->dev, nresults, nqueries, eps.data(), acc.data(), &n, nullptr);
+  if (rc && n > eps.size()) {  // the arrays were too short: n is the size needed
+    eps.resize(n);
+    acc.resize(n);
+    rc = ngt_amd_accuracy_table(ix->dev, nresults, nqueries, eps.data(), acc.data(), &n, nullptr);
+  }
+  if (rc) return amd_err();
+  std::vector<std::pair<float, double>> t(n);
+  for (uint32_t i = 0; i < n; i++) t[i] = {eps[i], acc[i]};
+  table = ngt_amd::accuracy_table_string(t);
+  return "";
+}
+
+// GraphOptimizer::optimizeSearchParameters (GraphOptimizer.h:302-384)
+std::string optimize_search_parameters(const CapiOptimizer& o, const std::string& path) {
+  if (o.search_parameter || o.prefetch_parameter)
+    return "Optimizer::execute: search-parameter optimization and prefetch-parameter optimization minimise measured "
+           "query time and are not implemented in the MI355X build; "
+           "ngt_optimizer_set_processing_modes(opt, false, false, true) generates the accuracy table alone.";
+  if (!o.accuracy_table) return "";
+  const std::string who = "Optimizer::execute: Cannot generate the accuracy table. ";
+  // (the reference opens the index outside its try block: there a missing index is reported without this prefix)
+  CapiIndex ix;
+  std::string e = ngt_amd::load_index(path, ix.host);
+  if (!e.empty()) return who + e;
+  std::string table;
+  e = accuracy_table_of(&ix, o.results, o.queries, table);
+  if (!e.empty()) return who + e;
+  ix.host.prop.kv["AccuracyTable"] = table;
+  e = ngt_amd::write_prf(path + "/prf", ix.host.prop);
+  if (!e.empty()) return "Optimizer::execute: Cannot save the index. " + path + e;
+  return "";
+}
+
+}  // namespace
+}  // extern "C++"
+
+bool ngt_optimizer_optimize_search_parameters(NGTOptimizer optimizer, const char* indexPath, NGTError error) {
+  if (optimizer == NULL) return !null_optimizer(error, __FUNCTION__);
+  if (indexPath == NULL) {
+    param_error(error, __FUNCTION__, "index path = 0");
+    return false;
+  }
+  try {
+    std::string e = optimize_search_parameters(*static_cast<CapiOptimizer*>(optimizer), indexPath);
+    if (!e.empty()) {
+      set_error(error, __FUNCTION__, e);
+      return false;
+    }
+  } catch (std::exception& err) {
+    set_error(error, __FUNCTION__, err.what());
+    return false;
+  }
+  return true;
+}
+
+bool ngt_generate_accuracy_table(NGTIndex index, size_t nOfResults, size_t nOfQueries, NGTError error) {
+  if (index == NULL) {
+    param_error(error, __FUNCTION__, "index = 0");
+    return false;
+  }
+  try {
+    CapiIndex* ix = static_cast<CapiIndex*>(index);
+    std::string table;
+    std::string e = accuracy_table_of(ix, nOfResults, nOfQueries, table);
+    if (!e.empty()) {
+      set_error(error, __FUNCTION__, e);
+      return false;
+    }
+    // the read lock was released: a write that got in between leaves a table of the state before it
+    std::unique_lock<std::shared_mutex> wl(ix->rw);
+    ix->host.prop.kv["AccuracyTable"] = table;
   } catch (std::exception& err) {
     set_error(error, __FUNCTION__, err.what());
     return false;

@@ -112,6 +112,18 @@ class DeviceIndex(object):
     def resolve_edge_size(self, edge_size, epsilon):
         return int(self.L.ngt_amd_resolve_edge_size(self.h, edge_size, epsilon))
 
+    def accuracy_table(self, num_of_results=20, num_of_queries=100):
+        """Optimizer::generateAccuracyTable on this index (ngt_amd_accuracy_table):
+        returns ([(epsilon float32, accuracy float), ...], maxEpsilon float32)."""
+        eps = np.zeros(1024, np.float32)
+        acc = np.zeros(1024, np.float64)
+        n = ctypes.c_uint32(len(eps))
+        me = ctypes.c_float(0.0)
+        _chk(self.L.ngt_amd_accuracy_table(self.h, num_of_results, num_of_queries,
+                                           eps.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
+                                           acc.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), byref(n), byref(me)))
+        return [(eps[i], float(acc[i])) for i in range(n.value)], np.float32(me.value)
+
     # ---- hot path -----------------------------------------------------------
     def search(self, queries, k=10, epsilon=0.1, radius=-1.0, edge_size=-1, seed_mode=SEED_TREE,
                seeds=None, counters=True, visited_hash_log2=0, distance_filter=0):

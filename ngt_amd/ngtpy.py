@@ -43,6 +43,11 @@ def accuracy_table(path):
             key, _, val = line.rstrip("\n").partition("\t")
             if key == "AccuracyTable":
                 text = val
+    return parse_accuracy_table(text)
+
+
+def parse_accuracy_table(text):
+    """Index::AccuracyTable::set of the table's string."""
     toks = [t for t in text.split(",") if t]
     if len(toks) < 2:
         return []
@@ -124,8 +129,20 @@ class Index(object):
         """The epsilon a search with this expected accuracy uses (the pybind
         argument is a float, widened to double for getEpsilon)."""
         if self._table is None:
-            self._table = accuracy_table(self._ix.path)
+            self._table = self._handle_table()
         return epsilon_from_expected_accuracy(self._table, float(np.float32(expected_accuracy)))
+
+    def _handle_table(self):
+        """The AccuracyTable of the open handle's property: the prf's as it was
+        opened, or the one generate_accuracy_table stored since."""
+        import ctypes
+        ix = self._ix
+        L = ix._L
+        ix._check(L.ngt_get_property(ix.index, ix.prop, ix.err), ix.err)
+        n = L.ngt_get_property_value(ix.prop, b"AccuracyTable", None, 0, ix.err)
+        buf = ctypes.create_string_buffer(max(n, 0) + 1)
+        L.ngt_get_property_value(ix.prop, b"AccuracyTable", buf, len(buf), ix.err)
+        return parse_accuracy_table(buf.value.decode())
 
     def linear_search(self, query, size=0, with_distance=True):
         """ngtpy.cpp:216-268: exact k-NN by full scan within the index's search
@@ -197,6 +214,19 @@ class Index(object):
                                           self._ix.err), self._ix.err)
         self._table = None
 
+    def generate_accuracy_table(self, num_of_results=20, num_of_queries=100):
+        """Optimizer::generateAccuracyTable (Optimizer.h:1495-1573) on the GPU
+        for the open index: what ``ngt optimize-search-parameters -m a``
+        computes.  The table goes into the index's property, so searches with
+        ``expected_accuracy`` and ``refine_anng(expected_accuracy=...)`` use it
+        at once and ``save`` writes it.  Returns the table as
+        ``[(epsilon, accuracy), ...]``."""
+        ix = self._ix
+        ix._check(ix._L.ngt_generate_accuracy_table(ix.index, int(num_of_results), int(num_of_queries), ix.err),
+                  ix.err)
+        self._table = self._handle_table()
+        return [(float(e), a) for e, a in self._table]
+
     def save(self):
         if self.read_only:
             raise NativeError("ngtpy::save: the index is read only")
@@ -211,7 +241,9 @@ class Optimizer(object):
     reference's argument names and defaults (negative values keep the
     optimizer's own defaults, GraphOptimizer.h:63-78, :545-591).  ``execute``
     runs edge and path adjustment on the MI355X; the three tuning steps have to
-    be switched off with ``set_processing_modes`` first."""
+    be switched off with ``set_processing_modes`` first.
+    ``optimize_search_parameters`` generates the accuracy table; search-parameter
+    and prefetch optimisation have to be off for it."""
 
     def __init__(self, num_of_outgoings=-1, num_of_incomings=-1, num_of_queries=-1, num_of_objects=-1,
                  low_accuracy_from=-1.0, low_accuracy_to=-1.0, high_accuracy_from=-1.0, high_accuracy_to=-1.0,
@@ -270,3 +302,9 @@ class Optimizer(object):
 
     def execute(self, in_path, out_path):
         self._check(self._L.ngt_optimizer_execute(self._opt, os.fsencode(in_path), os.fsencode(out_path), self._err))
+
+    def optimize_search_parameters(self, index_path):
+        """GraphOptimizer::optimizeSearchParameters (GraphOptimizer.h:302-384) with
+        accuracy-table generation alone: rewrites ``index_path``/prf with the
+        table ``ngt optimize-search-parameters -m a`` writes."""
+        self._check(self._L.ngt_optimizer_optimize_search_parameters(self._opt, os.fsencode(index_path), self._err))
