@@ -12,6 +12,7 @@
  *   setProcessingModes     :628-634
  *   execute                :230-300
  *   optimizeSearchParameters :302-384
+ *   optimizeNumberOfEdgesForANNG(path, parameter) :511-543
  *
  * Of the three tuning steps, searchParameterOptimization and
  * prefetchParameterOptimization minimise measured query time and are not
@@ -20,8 +21,14 @@
  * reconstruct-graph -s n` does.  optimizeSearchParameters(path) with
  * accuracyTableGeneration alone (`ngt optimize-search-parameters -m a`)
  * generates the accuracy table on the GPU and rewrites path/prf; it throws
- * while one of the other two is on.  adjustSearchCoefficients and
- * optimizeNumberOfEdgesForANNG are outside this build's scope.
+ * while one of the other two is on.  optimizeNumberOfEdgesForANNG(path,
+ * parameter) (`ngt optimize-#-of-edges`) runs its constructions, re-cuts and
+ * searches on the GPU, stores the new EdgeSizeForCreation in path/prf and
+ * returns it with the estimated accuracy; where the reference's estimate is
+ * undefined (it divides by a last sample's accuracy gain of 0 or less, or
+ * converts a negative or non-finite double to size_t) it throws the
+ * reference's "Cannot optimize the number of edges." with the reason.
+ * adjustSearchCoefficients is outside this build's scope.
  */
 #ifndef NGT_AMD_CXX_GRAPH_OPTIMIZER_H
 #define NGT_AMD_CXX_GRAPH_OPTIMIZER_H
@@ -45,6 +52,26 @@ class GraphOptimizer {
     set(outgoing, incoming, nofqs, nofrs, baseAccuracyFrom, baseAccuracyTo, rateAccuracyFrom, rateAccuracyTo, gte, m);
     logDisabled = unlog;
   }
+
+  struct ANNGEdgeOptimizationParameter {  // lib/NGT/GraphOptimizer.h:34-52
+    ANNGEdgeOptimizationParameter() { initialize(); }
+    void initialize() {
+      noOfQueries = 200;
+      noOfResults = 50;
+      noOfThreads = 16;
+      targetAccuracy = 0.9f;
+      targetNoOfObjects = 0;
+      noOfSampleObjects = 100000;
+      maxNoOfEdges = 100;
+    }
+    size_t noOfQueries;
+    size_t noOfResults;
+    size_t noOfThreads;
+    float targetAccuracy;
+    size_t targetNoOfObjects;
+    size_t noOfSampleObjects;
+    size_t maxNoOfEdges;
+  };
 
   void init() {
     numOfOutgoingEdges = 10;
@@ -102,6 +129,25 @@ class GraphOptimizer {
               ngt_optimizer_optimize_search_parameters(opt, outIndexPath.c_str(), err);
     ngt_destroy_optimizer(opt);
     if (!ok) err.raise("GraphOptimizer::optimizeSearchParameters");
+  }
+
+  std::pair<size_t, float> optimizeNumberOfEdgesForANNG(const std::string indexPath,
+                                                        ANNGEdgeOptimizationParameter &parameter) {
+    detail::Err err;
+    NGTAnngEdgeOptimizationParameter p = ngt_get_anng_edge_optimization_parameter();
+    p.no_of_queries = parameter.noOfQueries;
+    p.no_of_results = parameter.noOfResults;
+    p.no_of_threads = parameter.noOfThreads;
+    p.target_accuracy = parameter.targetAccuracy;
+    p.target_no_of_objects = parameter.targetNoOfObjects;
+    p.no_of_sample_objects = parameter.noOfSampleObjects;
+    p.max_of_no_of_edges = parameter.maxNoOfEdges;
+    p.log = false;
+    size_t edge = 0;
+    float accuracy = 0.0f;
+    if (!ngt_optimize_number_of_edges_with_result(indexPath.c_str(), p, &edge, &accuracy, err))
+      err.raise("GraphOptimizer::optimizeNumberOfEdgesForANNG");
+    return std::make_pair(edge, accuracy);
   }
 
   void execute(const std::string inIndexPath, const std::string outIndexPath) {

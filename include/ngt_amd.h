@@ -423,6 +423,84 @@ uint32_t ngt_amd_refine_fast_path_capacity(void);
 int ngt_amd_accuracy_table(ngt_amd_index *index, uint64_t nresults, uint64_t nqueries, float *eps_out,
                            double *acc_out, uint32_t *n, float *max_epsilon);
 
+/* ---- edge-count optimisation ---------------------------------------------- *
+ *   ngt_amd_recut_anng <- GraphReconstructor::reconstructANNGFromANNG
+ *   (lib/NGT/GraphReconstructor.h:721-801) on a host CSR graph (node v's list
+ *   ids/dists[offsets[v] .. offsets[v+1]), slot 0 the dummy, ids in [1, nrows)):
+ *   every list is emptied; for v ascending, v's list is walked in order and an
+ *   entry (m, d) with m < v goes to v's list as (m, d) and to m's list as
+ *   (v, d) until K such entries were taken; a distance below its predecessor's
+ *   (the first one's predecessor is 0) ends the walk of that list, as the
+ *   reference's swallowed exception does; then every list is sorted by
+ *   (distance, id) and an id equal to its predecessor's is dropped.  The result
+ *   equals the reference's edge for edge (-0 is returned as +0).  The call keeps
+ *   it for the calling thread, as ngt_amd_onng_reconstruct does;
+ *   ngt_amd_recut_get_graph copies it out (offsets [nrows + 1]).
+ *
+ *   ngt_amd_optimize_edges <- GraphOptimizer::optimizeNumberOfEdgesForANNG(index,
+ *   parameter) (lib/NGT/GraphOptimizer.h:386-509), what `ngt optimize-#-of-edges`
+ *   runs: no_of_queries stored objects drawn over a fresh process's rand()
+ *   stream become the queries and leave the repository; graph and tree are
+ *   discarded; samples of 12500, 25000, ... stored objects are constructed at
+ *   max_no_of_edges edges per node, each into the graph and tree the sample
+ *   before left; per sample a pseudo ground truth (the maxEpsilon loop of
+ *   ngt_amd_accuracy_table at no_of_results results) and, for K = 5, 10, 20,
+ *   30, ... <= max_no_of_edges, the sample's graph re-cut to K and one search
+ *   batch over all edges at epsilon 0, until the mean accuracy reaches
+ *   target_accuracy; then the estimate for target_no_of_objects.  The index has
+ *   its objects; `build` carries the creation properties (its
+ *   edge_size_for_creation is ignored).  Constructions run in a build session;
+ *   the sample's graph is uploaded once, every K is cut from it in HBM and
+ *   handed to the search as a device CSR.  On return -- success or failure --
+ *   the drawn objects' validity flags are cleared on the index, its graph is
+ *   the last re-cut and its tree the last sample's.  *edge is the estimate
+ *   before the path form's rounding (ngt_amd_round_edges).
+ *   Two deliberate differences: the work guard of ngt_amd_accuracy_table in
+ *   place of the reference's wall-clock clause; and where the reference's
+ *   estimate converts a negative, non-finite or too large double to size_t --
+ *   the last sample's accuracy gain per edge, which it divides by, is 0 when
+ *   that sample stopped at K = 5 -- the call fails with the reference's "Cannot
+ *   optimize the number of edges." and a clause that says why.
+ *   samples holds *nsamples entries on entry (both nullable); *nsamples is the
+ *   number of samples run on return (entries beyond the capacity are dropped,
+ *   as are steps beyond NGT_AMD_EDGE_STEPS).  ngt_amd_optimize_edges_last_trace
+ *   returns the samples of the calling thread's last optimisation the same
+ *   way, also after ngt_optimize_number_of_edges. */
+#define NGT_AMD_EDGE_STEPS 32
+typedef struct {
+  uint64_t no_of_queries;         /* noOfQueries (200)                              */
+  uint64_t no_of_results;         /* noOfResults (50)                               */
+  uint64_t no_of_threads;         /* noOfThreads (16): accepted, unused             */
+  float target_accuracy;          /* targetAccuracy (0.9)                           */
+  int32_t reserved;
+  uint64_t target_no_of_objects;  /* targetNoOfObjects (0 = the repository size)    */
+  uint64_t no_of_sample_objects;  /* noOfSampleObjects (100000)                     */
+  uint64_t max_no_of_edges;       /* maxNoOfEdges (100)                             */
+  ngt_amd_build_params build;     /* the prf's creation properties                  */
+} ngt_amd_edge_params;
+typedef struct {
+  uint64_t objects;               /* noOfObjects of the sample                      */
+  uint64_t edge;                  /* the K it stopped at                            */
+  double accuracy, gain;          /* its accuracy there, the gain per edge          */
+  float max_epsilon;              /* of the pseudo ground truth                     */
+  int32_t guard_fired;            /* the work guard ended the maxEpsilon loop       */
+  uint32_t nsteps;                /* edge counts tried                              */
+  uint32_t reserved;
+  uint64_t step_edge[NGT_AMD_EDGE_STEPS];
+  double step_accuracy[NGT_AMD_EDGE_STEPS];
+  double build_ms, recut_ms, search_ms; /* wall time: construction, re-cuts (with
+                                     the hand-over to the search), search batches  */
+} ngt_amd_edge_sample;
+int ngt_amd_recut_anng(int device, const uint64_t *offsets, const uint32_t *ids, const float *dists,
+                       uint64_t nrows, uint32_t K, uint64_t *out_nedges);
+int ngt_amd_recut_get_graph(uint64_t *offsets, uint32_t *ids, float *dists);
+int ngt_amd_optimize_edges(ngt_amd_index *index, const ngt_amd_edge_params *params, uint64_t *edge,
+                           float *accuracy, ngt_amd_edge_sample *samples, uint32_t *nsamples);
+int ngt_amd_optimize_edges_last_trace(ngt_amd_edge_sample *samples, uint32_t *nsamples);
+/* (edge + 10) / 5 * 5, capped at max_no_of_edges: the EdgeSizeForCreation the
+ * path form stores (GraphOptimizer.h:528-531). */
+uint64_t ngt_amd_round_edges(uint64_t edge, uint64_t max_no_of_edges);
+
 /* ---- repository sharding (one shard per GPU) ------------ *
  * Merge of per-shard result lists gathered from every rank (RCCL all-gather
  * over xGMI): the k best (distance, global id) per query, the ordering of

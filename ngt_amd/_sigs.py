@@ -46,6 +46,28 @@ class OnngStats(Structure):
                 ("max_passes_per_rank", c_uint32), ("ranks", c_uint32), ("reserved", c_uint32)]
 
 
+class EdgeParams(Structure):
+    _fields_ = [("no_of_queries", c_uint64), ("no_of_results", c_uint64), ("no_of_threads", c_uint64),
+                ("target_accuracy", c_float), ("reserved", c_int32), ("target_no_of_objects", c_uint64),
+                ("no_of_sample_objects", c_uint64), ("max_no_of_edges", c_uint64), ("build", BuildParams)]
+
+
+EDGE_STEPS = 32
+
+
+class EdgeSample(Structure):
+    _fields_ = [("objects", c_uint64), ("edge", c_uint64), ("accuracy", c_double), ("gain", c_double),
+                ("max_epsilon", c_float), ("guard_fired", c_int32), ("nsteps", c_uint32), ("reserved", c_uint32),
+                ("step_edge", c_uint64 * EDGE_STEPS), ("step_accuracy", c_double * EDGE_STEPS),
+                ("build_ms", c_double), ("recut_ms", c_double), ("search_ms", c_double)]
+
+
+class NGTAnngEdgeOptimizationParameter(Structure):
+    _fields_ = [("no_of_queries", c_size_t), ("no_of_results", c_size_t), ("no_of_threads", c_size_t),
+                ("target_accuracy", c_float), ("target_no_of_objects", c_size_t),
+                ("no_of_sample_objects", c_size_t), ("max_of_no_of_edges", c_size_t), ("log", c_bool)]
+
+
 class NGTQGQuery(Structure):
     _fields_ = [("query", POINTER(c_float)), ("size", c_size_t), ("epsilon", c_float),
                 ("result_expansion", c_float), ("radius", c_float)]
@@ -124,6 +146,11 @@ def declare(L):
         "ngt_amd_onng_fast_path_capacity": (c_uint32, []),
         "ngt_amd_accuracy_table": (c_int, [vp, c_uint64, c_uint64, POINTER(c_float), POINTER(c_double),
                                            POINTER(c_uint32), POINTER(c_float)]),
+        "ngt_amd_recut_anng": (c_int, [c_int, vp, vp, vp, c_uint64, c_uint32, u64p]),
+        "ngt_amd_recut_get_graph": (c_int, [vp, vp, vp]),
+        "ngt_amd_optimize_edges": (c_int, [vp, POINTER(EdgeParams), u64p, f32p, POINTER(EdgeSample), u32p]),
+        "ngt_amd_optimize_edges_last_trace": (c_int, [POINTER(EdgeSample), u32p]),
+        "ngt_amd_round_edges": (c_uint64, [c_uint64, c_uint64]),
         "ngt_amd_refine_anng": (c_int, [vp, vp, vp, vp, c_uint64, POINTER(RefineParams), u64p]),
         "ngt_amd_refine_merge": (c_int, [c_int, vp, vp, vp, c_uint64, c_uint32, c_uint32, c_uint32, vp, vp, vp,
                                          c_int, u64p]),
@@ -233,6 +260,10 @@ def declare(L):
         "ngt_optimizer_get": (c_bool, [vp, POINTER(c_double), vp]),
         "ngt_optimizer_optimize_search_parameters": (c_bool, [vp, c_char_p, vp]),
         "ngt_generate_accuracy_table": (c_bool, [vp, c_size_t, c_size_t, vp]),
+        "ngt_get_anng_edge_optimization_parameter": (NGTAnngEdgeOptimizationParameter, []),
+        "ngt_optimize_number_of_edges": (c_bool, [c_char_p, NGTAnngEdgeOptimizationParameter, vp]),
+        "ngt_optimize_number_of_edges_with_result": (c_bool, [c_char_p, NGTAnngEdgeOptimizationParameter,
+                                                              POINTER(c_size_t), f32p, vp]),
         "ngt_refine_anng": (c_bool, [vp, c_float, c_float, c_int, c_int, c_size_t, vp]),
         "ngt_get_edges": (c_bool, [vp, c_uint, vp, vp]),
         "ngt_get_object_repository_size": (c_uint32, [vp, vp]),

@@ -112,9 +112,7 @@ std::vector<float> accuracy_parse_queries(const std::string& text) {
   return out;
 }
 
-namespace {
-
-std::string run_batch(const AccuracySearch& search, AccuracyBatch& b) {
+std::string accuracy_run_batch(const AccuracySearch& search, AccuracyBatch& b) {
   b.ids.assign((size_t)b.nq * b.size, 0);
   b.dists.assign((size_t)b.nq * b.size, 0.0f);
   b.n.assign(b.nq, 0);
@@ -126,16 +124,13 @@ std::string run_batch(const AccuracySearch& search, AccuracyBatch& b) {
   return "";
 }
 
+namespace {
 double printed(float d) { return strtod(format_stream(d).c_str(), nullptr); }
-
-struct GroundTruth {  // per query: ids and distances as the evaluation output prints them
-  std::vector<std::vector<uint32_t>> ids;
-  std::vector<std::vector<double>> dists;
-};
+}  // namespace
 
 // evaluate (:175-226) of one epsilon's results against the ground truth;
 // MeasuredValue::meanAccuracy is a float (:37).
-std::string mean_accuracy(const GroundTruth& gt, const AccuracyBatch& b, double& accuracy) {
+std::string accuracy_evaluate(const AccuracyGroundTruth& gt, const AccuracyBatch& b, double& accuracy) {
   size_t size = 0;  // checkAndGetSize (:280-343): the first result size, raised by a larger one
   for (uint32_t q = 0; q < b.nq; q++)
     if (b.n[q] > size) size = b.n[q];
@@ -164,19 +159,16 @@ std::string mean_accuracy(const GroundTruth& gt, const AccuracyBatch& b, double&
   return "";
 }
 
-}  // namespace
-
-std::string accuracy_generate(const AccuracySearch& search, const std::vector<float>& queries, uint32_t dim,
-                              int object_type, size_t nresults, double guard,
-                              std::vector<std::pair<float, double>>& table, AccuracyTrace* trace) {
-  table.clear();
+std::string accuracy_pseudo_ground_truth(const AccuracySearch& search, const std::vector<float>& queries, uint32_t dim,
+                                         int object_type, size_t nresults, double guard, std::vector<float>& rounded,
+                                         AccuracyGroundTruth& gt, AccuracyTrace& tr) {
   if (dim == 0 || queries.empty() || queries.size() % dim) return "Optimizer: no query was extracted";
   const uint32_t nq = (uint32_t)(queries.size() / dim);
-  AccuracyTrace tr;
+  tr = AccuracyTrace();
+  gt = AccuracyGroundTruth();
   AccuracyBatch b;
   b.nq = nq;
   b.dim = dim;
-
   // generatePseudoGroundTruth (:1425-1481): the unrounded queries, nresults
   // results, the property's edge size
   float maxEpsilon = 0.0;
@@ -190,7 +182,7 @@ std::string accuracy_generate(const AccuracySearch& search, const std::vector<fl
       b.size = nresults;
       b.epsilon = e;
       b.edge_size = -1;
-      std::string err = run_batch(search, b);
+      std::string err = accuracy_run_batch(search, b);
       if (!err.empty()) return err;
       bool identity = true;
       for (uint32_t idx = 0; idx < nq; idx++) {
@@ -221,17 +213,16 @@ std::string accuracy_generate(const AccuracySearch& search, const std::vector<fl
   tr.max_epsilon = maxEpsilon;
 
   // from here on the queries are the ones the query stream's text gives back
-  const std::vector<float> rounded = accuracy_parse_queries(accuracy_query_text(queries, dim, object_type));
+  rounded = accuracy_parse_queries(accuracy_query_text(queries, dim, object_type));
   if (rounded.size() != queries.size()) return "Optimizer: the query stream does not hold the extracted queries";
 
   // createGroundTruth (:1223-1229, :1485-1491): all edges, epsilon = maxEpsilon
-  GroundTruth gt;
   {
     b.queries = rounded.data();
     b.size = nresults;
     b.epsilon = maxEpsilon;
     b.edge_size = 0;
-    std::string err = run_batch(search, b);
+    std::string err = accuracy_run_batch(search, b);
     if (!err.empty()) return err;
     gt.ids.resize(nq);
     gt.dists.resize(nq);
@@ -241,6 +232,27 @@ std::string accuracy_generate(const AccuracySearch& search, const std::vector<fl
         gt.dists[q].push_back(printed(b.dists[(size_t)q * b.size + j]));
       }
   }
+  return "";
+}
+
+std::string accuracy_generate(const AccuracySearch& search, const std::vector<float>& queries, uint32_t dim,
+                              int object_type, size_t nresults, double guard,
+                              std::vector<std::pair<float, double>>& table, AccuracyTrace* trace) {
+  table.clear();
+  if (dim == 0 || queries.empty() || queries.size() % dim) return "Optimizer: no query was extracted";
+  const uint32_t nq = (uint32_t)(queries.size() / dim);
+  AccuracyTrace tr;
+  AccuracyBatch b;
+  b.nq = nq;
+  b.dim = dim;
+
+  std::vector<float> rounded;
+  AccuracyGroundTruth gt;
+  {
+    std::string err = accuracy_pseudo_ground_truth(search, queries, dim, object_type, nresults, guard, rounded, gt, tr);
+    if (!err.empty()) return err;
+  }
+  const float maxEpsilon = tr.max_epsilon;
 
   // the sweep (:1514-1554)
   std::map<float, double> map;
@@ -256,9 +268,9 @@ std::string accuracy_generate(const AccuracySearch& search, const std::vector<fl
         b.size = kAccuracySweepSize;
         b.epsilon = epsilon;
         b.edge_size = -1;
-        std::string err = run_batch(search, b);
+        std::string err = accuracy_run_batch(search, b);
         if (!err.empty()) return err;
-        err = mean_accuracy(gt, b, accuracy);
+        err = accuracy_evaluate(gt, b, accuracy);
         if (!err.empty()) return err;
         map.insert(std::make_pair(epsilon, accuracy));
       } else {

@@ -69,6 +69,22 @@ struct AccuracyTrace {
   bool guard_fired = false;  // the work guard, not the identity rule, ended the maxEpsilon loop
 };
 
+// The parts the edge-count optimisation (edge_optimizer.h) shares with the
+// table: one batch with its outputs sized and checked; the maxEpsilon loop and
+// the pseudo ground truth of generatePseudoGroundTruth (:1425-1493) -- `rounded`
+// receives the queries the query stream's text gives back, which every later
+// search takes; and evaluate (:175-226) of one batch against that ground truth
+// over the batch's own result size (a float mean, returned as double).
+struct AccuracyGroundTruth {  // per query: ids and distances as the evaluation output prints them
+  std::vector<std::vector<uint32_t>> ids;
+  std::vector<std::vector<double>> dists;
+};
+std::string accuracy_run_batch(const AccuracySearch& search, AccuracyBatch& b);
+std::string accuracy_pseudo_ground_truth(const AccuracySearch& search, const std::vector<float>& queries, uint32_t dim,
+                                         int object_type, size_t nresults, double guard, std::vector<float>& rounded,
+                                         AccuracyGroundTruth& gt, AccuracyTrace& trace);
+std::string accuracy_evaluate(const AccuracyGroundTruth& gt, const AccuracyBatch& b, double& accuracy);
+
 // The whole procedure on extracted queries.  guard <= 0 leaves the work guard
 // out (the identity rule and e < 10 alone).
 std::string accuracy_generate(const AccuracySearch& search, const std::vector<float>& queries, uint32_t dim,

@@ -25,6 +25,7 @@
 #include "../../include/ngt_amd.h"
 #include "accuracy_table.h"
 #include "coalesce.h"
+#include "edge_optimizer.h"
 #include "index_io.h"
 
 using ngt_amd::HostIndex;
@@ -1528,9 +1529,100 @@ NGTAnngEdgeOptimizationParameter ngt_get_anng_edge_optimization_parameter() {
   p.log = false;
   return p;
 }
-bool ngt_optimize_number_of_edges(const char*, NGTAnngEdgeOptimizationParameter, NGTError error) {
-  set_error(error, __FUNCTION__, kNotImplemented);
-  return false;
+// ---- edge-count optimisation (GraphOptimizer::optimizeNumberOfEdgesForANNG(path,
+// parameter), GraphOptimizer.h:511-543)
+extern "C++" {
+namespace {
+
+std::string optimize_number_of_edges(const std::string& path, const NGTAnngEdgeOptimizationParameter& parameter,
+                                     size_t& edge, float& accuracy) {
+  CapiIndex ix;
+  std::string e = ngt_amd::load_index(path, ix.host);
+  if (!e.empty()) return e;
+  HostIndex& h = ix.host;
+  if (h.prop.index_type != 0)
+    return "Optimizer::optimizeNumberOfEdgesForANNG: the MI355X build takes GraphAndTree indexes only";
+  if (h.prop.graph_type != 1) return "Optimizer::optimizeNumberOfEdgesForANNG: the MI355X build constructs ANNGs only";
+  {
+    // what ends the call before any construction is decided here, on the host
+    // mirror and before the device copy exists: the query draw's refusal and
+    // fewer than two samples
+    const std::function<int()> next = ngt_amd::edge_fresh_rand();
+    std::vector<uint8_t> valid = h.valid;
+    std::vector<float> queries;
+    e = ngt_amd::edge_draw_queries(next,
+                                   [&](uint64_t id) -> const void* { return h.rows.data() + id * h.row_bytes; }, valid,
+                                   h.nrows, (uint32_t)h.prop.object_dimension(), h.prop.object_type,
+                                   parameter.no_of_queries, queries, nullptr);
+    if (!e.empty()) return e;
+    size_t targetNo = 12500, nsamples = 0;
+    for (; targetNo <= h.nrows && targetNo <= parameter.no_of_sample_objects; targetNo *= 2) nsamples++;
+    if (nsamples < 2) {
+      size_t none = 0;
+      float nothing = 0.0f;
+      return ngt_amd::edge_estimate({}, 0, 0.0f, h.nrows, targetNo, none, nothing);
+    }
+  }
+  // the procedure discards graph and tree: the device copy takes the objects alone
+  h.edge_off.assign(h.nrows + 1, 0);
+  h.edges.clear();
+  h.edge_dists.clear();
+  h.tree = ngt_amd::HostTree();
+  ix.device_stale = true;
+  e = rebuild_device(&ix);
+  if (!e.empty()) return e;
+  ngt_amd_edge_params p{};
+  p.no_of_queries = parameter.no_of_queries;
+  p.no_of_results = parameter.no_of_results;
+  p.no_of_threads = parameter.no_of_threads;
+  p.target_accuracy = parameter.target_accuracy;
+  p.target_no_of_objects = parameter.target_no_of_objects;
+  p.no_of_sample_objects = parameter.no_of_sample_objects;
+  p.max_no_of_edges = parameter.max_of_no_of_edges;
+  p.build.edge_size_for_creation = h.prop.edge_size_for_creation;
+  p.build.edge_size_for_search = h.prop.edge_size_for_search;
+  p.build.batch_size_for_creation = h.prop.batch_size_for_creation;
+  p.build.seed_size = h.prop.seed_size;
+  p.build.epsilon_for_creation = (float)h.prop.epsilon_for_creation;
+  uint64_t est = 0;
+  if (ngt_amd_optimize_edges(ix.dev, &p, &est, &accuracy, nullptr, nullptr)) return amd_err();
+  edge = ngt_amd_round_edges(est, parameter.max_of_no_of_edges);
+  h.prop.edge_size_for_creation = (int32_t)edge;
+  e = ngt_amd::write_prf(path + "/prf", h.prop);  // saveProperty: grp, obj and tre stay
+  if (!e.empty()) return e;
+  return "";
+}
+
+}  // namespace
+}  // extern "C++"
+
+bool ngt_optimize_number_of_edges_with_result(const char* indexPath, NGTAnngEdgeOptimizationParameter parameter,
+                                              size_t* edge, float* accuracy, NGTError error) {
+  const char* func = "ngt_optimize_number_of_edges";
+  if (indexPath == NULL) {
+    param_error(error, func, "index path = 0");
+    return false;
+  }
+  try {
+    size_t n = 0;
+    float a = 0.0f;
+    std::string e = optimize_number_of_edges(indexPath, parameter, n, a);
+    if (!e.empty()) {
+      set_error(error, func, e);
+      return false;
+    }
+    if (parameter.log) std::cerr << "the optimized number of edges is" << n << "(" << a << ")" << std::endl;
+    if (edge) *edge = n;
+    if (accuracy) *accuracy = a;
+  } catch (std::exception& err) {
+    set_error(error, func, err.what());
+    return false;
+  }
+  return true;
+}
+
+bool ngt_optimize_number_of_edges(const char* indexPath, NGTAnngEdgeOptimizationParameter parameter, NGTError error) {
+  return ngt_optimize_number_of_edges_with_result(indexPath, parameter, NULL, NULL, error);
 }
 
 // ---- extensions --------------------------------------------------------------

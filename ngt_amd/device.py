@@ -124,6 +124,33 @@ class DeviceIndex(object):
                                            acc.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), byref(n), byref(me)))
         return [(eps[i], float(acc[i])) for i in range(n.value)], np.float32(me.value)
 
+    def optimize_edges(self, num_of_queries=200, num_of_results=50, target_accuracy=0.9, target_num_of_objects=0,
+                       num_of_sample_objects=100000, max_num_of_edges=100, edge_size_for_search=40,
+                       batch_size_for_creation=200, seed_size=10, epsilon_for_creation=0.1):
+        """GraphOptimizer::optimizeNumberOfEdgesForANNG on this index's objects
+        (ngt_amd_optimize_edges): returns (estimated edges before the path form's
+        rounding, estimated accuracy float32, [per sample a dict of the trace])."""
+        from ._sigs import EDGE_STEPS, BuildParams, EdgeParams, EdgeSample
+        p = EdgeParams(num_of_queries, num_of_results, 16, target_accuracy, 0, target_num_of_objects,
+                       num_of_sample_objects, max_num_of_edges,
+                       BuildParams(max_num_of_edges, edge_size_for_search, batch_size_for_creation, seed_size,
+                                   epsilon_for_creation, 0))
+        samples = (EdgeSample * 16)()
+        n = ctypes.c_uint32(16)
+        edge = ctypes.c_uint64(0)
+        acc = ctypes.c_float(0.0)
+        rc = self.L.ngt_amd_optimize_edges(self.h, byref(p), byref(edge), byref(acc), samples, byref(n))
+        trace = []
+        for s in samples[:min(n.value, 16)]:
+            steps = min(s.nsteps, EDGE_STEPS)
+            trace.append({"objects": s.objects, "edge": s.edge, "accuracy": s.accuracy, "gain": s.gain,
+                          "max_epsilon": np.float32(s.max_epsilon), "guard_fired": bool(s.guard_fired),
+                          "steps": [(s.step_edge[i], s.step_accuracy[i]) for i in range(steps)],
+                          "build_ms": s.build_ms, "recut_ms": s.recut_ms, "search_ms": s.search_ms})
+        self.last_edge_trace = trace
+        _chk(rc)
+        return edge.value, np.float32(acc.value), trace
+
     # ---- hot path -----------------------------------------------------------
     def search(self, queries, k=10, epsilon=0.1, radius=-1.0, edge_size=-1, seed_mode=SEED_TREE,
                seeds=None, counters=True, visited_hash_log2=0, distance_filter=0):

@@ -243,7 +243,8 @@ class Optimizer(object):
     runs edge and path adjustment on the MI355X; the three tuning steps have to
     be switched off with ``set_processing_modes`` first.
     ``optimize_search_parameters`` generates the accuracy table; search-parameter
-    and prefetch optimisation have to be off for it."""
+    and prefetch optimisation have to be off for it.
+    ``optimize_number_of_edges_for_anng`` is ``ngt optimize-#-of-edges``."""
 
     def __init__(self, num_of_outgoings=-1, num_of_incomings=-1, num_of_queries=-1, num_of_objects=-1,
                  low_accuracy_from=-1.0, low_accuracy_to=-1.0, high_accuracy_from=-1.0, high_accuracy_to=-1.0,
@@ -308,3 +309,33 @@ class Optimizer(object):
         accuracy-table generation alone: rewrites ``index_path``/prf with the
         table ``ngt optimize-search-parameters -m a`` writes."""
         self._check(self._L.ngt_optimizer_optimize_search_parameters(self._opt, os.fsencode(index_path), self._err))
+
+    def optimize_number_of_edges_for_anng(self, path, num_of_queries=-1, num_of_results=-1, num_of_threads=-1,
+                                          target_accuracy=-1.0, target_num_of_objects=-1, num_of_sample_objects=-1,
+                                          max_num_of_edges=-1):
+        """GraphOptimizer::optimizeNumberOfEdgesForANNG(path, parameter)
+        (ngtpy.cpp:353-378; negative values, and zeros where the reference says
+        so, keep the defaults): what ``ngt optimize-#-of-edges`` runs.  Rewrites
+        ``path``/prf with the new EdgeSizeForCreation and returns it."""
+        import ctypes
+        p = self._L.ngt_get_anng_edge_optimization_parameter()
+        if num_of_queries > 0:
+            p.no_of_queries = int(num_of_queries)
+        if num_of_results > 0:
+            p.no_of_results = int(num_of_results)
+        if num_of_threads >= 0:
+            p.no_of_threads = int(num_of_threads)
+        if target_accuracy > 0.0:
+            p.target_accuracy = target_accuracy
+        if target_num_of_objects >= 0:
+            p.target_no_of_objects = int(target_num_of_objects)
+        if num_of_sample_objects > 0:
+            p.no_of_sample_objects = int(num_of_sample_objects)
+        if max_num_of_edges > 0:
+            p.max_of_no_of_edges = int(max_num_of_edges)
+        p.log = not bool(self.get()["log_disabled"])
+        edge = ctypes.c_size_t(0)
+        acc = ctypes.c_float(0.0)
+        self._check(self._L.ngt_optimize_number_of_edges_with_result(os.fsencode(path), p, ctypes.byref(edge),
+                                                                      ctypes.byref(acc), self._err))
+        return int(edge.value)
