@@ -354,6 +354,9 @@ extern "C" int ngt_amd_build_insert(ngt_amd_index* ix, uint64_t first_id, uint64
     ta.pre_leaf = d_pleaf.p;
     ta.pre_count = d_pcnt.p;
     ta.pre_dist = d_pdist.p;
+    // NGT_AMD_BUILD_REPL_CAP: a smaller table, so that small batches fill it
+    ta.repl_cap = 256;
+    if (const char* v = ngt_amd::knob("NGT_AMD_BUILD_REPL_CAP")) ta.repl_cap = (uint32_t)std::min(256, std::max(0, atoi(v)));
     ta.n = n;
     ta.error = ix->error.p;
     // the merged lists go to the host while the tree insertion runs

@@ -278,6 +278,7 @@ struct TreeBuildArgs {
   const uint32_t* pre_leaf;
   const uint32_t* pre_count;
   const float* pre_dist;
+  uint32_t repl_cap;             // entries of the LDS table of leaves split in this batch (<= 256)
   uint32_t n;
   int* error;
 };
