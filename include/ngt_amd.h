@@ -706,6 +706,19 @@ int ngt_amd_ngtq_search_device(ngt_amd_index *index, const ngt_amd_ngtq_search_p
                                const void *d_queries, uint64_t query_bytes, uint32_t nq,
                                uint32_t *d_ids, float *d_dists, uint32_t *d_n, void *stream);
 
+/* ---- testing only -------------------------------------------------------- *
+ * One wave drives the unchecked set of the latency and NGTQG search kernels
+ * (csrc/unchecked_set.h; tagged / trim choose the instantiation) through
+ * script [n]: a non-zero word inserts that key, a zero pops.  popped [n] takes
+ * one key per pop (0 when the set gave none).  tail_cap 64..4096 keys, expr the
+ * exploration radius.  A tagged set tags head lane tag_lane[i] after step i
+ * (>= 64: none) and logs events [3 n][2] as {kind << 32 | tag, key}: 1 tagged,
+ * 2 popped with its tag, 3 orphaned.  Host pointers. */
+int ngt_amd_test_unchecked_set(int device, int tagged, int trim, const uint64_t *script,
+                               const uint8_t *tag_lane, uint32_t n, uint32_t tail_cap,
+                               uint32_t spill_cap, float expr, uint64_t *popped, uint32_t *npopped,
+                               uint64_t *events, uint32_t *nevents, uint32_t *maxq, uint32_t *error);
+
 #ifdef __cplusplus
 }
 #endif

@@ -189,6 +189,8 @@ def declare(L):
         "ngt_amd_ngtq_search": (c_int, [vp, POINTER(NgtqSearchParams), vp, c_uint32, vp, vp, vp]),
         "ngt_amd_ngtq_search_device": (c_int, [vp, POINTER(NgtqSearchParams), vp, c_uint64, c_uint32, vp, vp, vp,
                                                vp]),
+        "ngt_amd_test_unchecked_set": (c_int, [c_int, c_int, c_int, vp, vp, c_uint32, c_uint32, c_uint32, c_float,
+                                               vp, vp, vp, vp, vp, vp]),
         # ---- include/NGT/Capi.h
         "ngt_open_index": (vp, [c_char_p, vp]),
         "ngt_create_graph_and_tree": (vp, [c_char_p, vp, vp]),

@@ -28,6 +28,7 @@
 #include "ngt_device.h"
 #include "ngt_kernels.h"
 #include "search_common.h"
+#include "unchecked_set.h"
 
 // 1: the previous all-VALU cross-lane sum (v_perm packing + reduce-scatter)
 #ifndef NGT_AMD_QG_VALU_REDUCE
@@ -939,7 +940,7 @@ __global__ void __launch_bounds__(64, NGT_AMD_QG_WPE) ngt_qg_search_kernel(QgSea
     if (lane == 0) a.slot_epoch[slot] = epoch;
 
     bool bitmap_mode = !use_hash;
-    uint32_t nvisited = 0, nres = 0, maxq = 0;
+    uint32_t nvisited = 0, nres = 0;
     uint64_t nadc = 0, nacc = 0, nexp = 0, nexact = 0, nblk = 0;
     uint64_t t_pop = 0, t_ids = 0, t_adc = 0, t_acc = 0, t_last = 0;
     (void)t_pop; (void)t_ids; (void)t_adc; (void)t_acc; (void)t_last;
@@ -947,208 +948,12 @@ __global__ void __launch_bounds__(64, NGT_AMD_QG_WPE) ngt_qg_search_kernel(QgSea
     float radius = a.radius;
     float expr = __fmul_rn(a.coef, radius);
 
-    // ---- the unchecked set: a sorted head of the 64 smallest keys in
-    // registers (lane i = i-th smallest, hn keys) < B <= an unsorted LDS tail
-    // (st.cq, ntail keys) < T <= an HBM spill (nspill keys) -- the latency
-    // kernel's form (search_lat.hip), so a pop is a lane shift and never scans
-    // anything: a quantized graph over 12.5M objects keeps ~40k unchecked keys
-    // per query, and the chunk-minimum scans of a flat spill were most of its
-    // expansions' time.  Exact throughout; keys beyond the exploration radius
-    // are dropped when the tail fills (they can never be popped,
-    // QuantizedGraph.h:226-229 / Graph.cpp:433-435).
-    uint64_t hk = ~0ull, B = ~0ull, T = ~0ull;
-    uint32_t hn = 0, ntail = 0, nspill = 0;
-    uint64_t* tail = st.cq;
-    uint32_t ntrim = 0;  // spill trims (counter 7)
-    // a full spill first drops its keys beyond the exploration radius (they
-    // can never be popped: expr only shrinks); the capacity error is left for
-    // a spill still full of keys within it
-    auto spill_trim = [&]() {
-      const uint64_t lim = ((uint64_t)ord_of(expr) << 32) | 0xffffffffull;
-      uint32_t out = 0;
-      for (uint32_t b0 = 0; b0 < nspill; b0 += 64) {
-        const uint32_t i = b0 + (uint32_t)lane;
-        const uint64_t key = i < nspill ? spill[i] : ~0ull;
-        const bool kp = i < nspill && key <= lim;
-        const uint64_t km = ballot64(kp);
-        __builtin_amdgcn_wave_barrier();
-        if (kp) spill[out + mbcnt(km)] = key;
-        __builtin_amdgcn_wave_barrier();
-        out += (uint32_t)__popcll(km);
-      }
-      nspill = out;
-      ntrim++;
-    };
-    auto spill_push = [&](uint64_t key) {
-      if (nspill >= a.spill_cap) spill_trim();
-      if (nspill >= a.spill_cap) {
-        if (lane == 0) atomicOr(a.error, 1);
-      } else {
-        if (lane == 0) spill[nspill] = key;
-        nspill++;
-      }
-    };
-    auto tail_room = [&]() {
-      uint32_t out = 0;
-      for (uint32_t b0 = 0; b0 < ntail; b0 += 64) {
-        const uint32_t i = b0 + (uint32_t)lane;
-        const uint64_t key = i < ntail ? tail[i] : ~0ull;
-        const bool keep = i < ntail && key_dist(key) <= expr;
-        const uint64_t km = ballot64(keep);
-        __builtin_amdgcn_wave_barrier();
-        if (keep) tail[out + mbcnt(km)] = key;
-        __builtin_amdgcn_wave_barrier();
-        out += (uint32_t)__popcll(km);
-      }
-      ntail = out;
-      const uint32_t keep = a.cq_cap / 2;
-      if (ntail <= keep) return;
-      const uint64_t l = lat_select(tail, ntail, keep, ~0ull, hist);
-      out = 0;
-      for (uint32_t b0 = 0; b0 < ntail; b0 += 64) {
-        const uint32_t i = b0 + (uint32_t)lane;
-        const uint64_t key = i < ntail ? tail[i] : ~0ull;
-        const bool mv = i < ntail && key >= l;
-        const bool kp = i < ntail && key < l;
-        const uint64_t mm = ballot64(mv), km = ballot64(kp);
-        const uint32_t nm = (uint32_t)__popcll(mm);
-        if (nspill + nm > a.spill_cap) spill_trim();
-        if (nspill + nm > a.spill_cap) {
-          if (lane == 0) atomicOr(a.error, 1);
-        } else if (mv) {
-          spill[nspill + mbcnt(mm)] = key;
-        }
-        if (nspill + nm <= a.spill_cap) nspill += nm;
-        __builtin_amdgcn_wave_barrier();
-        if (kp) tail[out + mbcnt(km)] = key;
-        __builtin_amdgcn_wave_barrier();
-        out += (uint32_t)__popcll(km);
-      }
-      if ((out == 0u || out > keep) && lane == 0) atomicOr(a.error, 32);  // selection check
-      ntail = out;
-      T = l;
-    };
-    auto tail_push = [&](uint64_t key) {
-      if (key >= T) {
-        spill_push(key);
-      } else {
-        if (ntail >= a.cq_cap) tail_room();
-        if (key >= T) {
-          spill_push(key);
-        } else {
-          if (lane == 0) tail[ntail] = key;
-          ntail++;
-        }
-      }
-      __builtin_amdgcn_wave_barrier();
-    };
-    auto insert_key = [&](uint64_t key) {
-      if (key < B) {
-        const uint32_t pos = (uint32_t)__popcll(ballot64((uint32_t)lane < hn && hk < key));
-        if (hn == 64u) {
-          // the head is full: its largest key (or this one) moves to the tail
-          if (pos == 64u) {
-            B = key;
-            tail_push(key);
-          } else {
-            const uint64_t e = readlane_u64(hk, 63);
-            const uint64_t uk = wave_up1_u64(hk);
-            if ((uint32_t)lane > pos) hk = uk;
-            if ((uint32_t)lane == pos) hk = key;
-            B = e;
-            tail_push(e);
-          }
-        } else {
-          const uint64_t uk = wave_up1_u64(hk);
-          if ((uint32_t)lane > pos && (uint32_t)lane <= hn) hk = uk;
-          if ((uint32_t)lane == pos) hk = key;
-          hn++;
-        }
-      } else {
-        tail_push(key);
-      }
-      const uint32_t q = hn + ntail + nspill;
-      if (q > maxq) maxq = q;
-    };
-    // an empty tail takes the smallest spill keys within the radius (the ones
-    // beyond it are dropped)
-    auto refill_tail = [&]() {
-      const uint32_t want = a.cq_cap / 2;
-      const uint64_t lim = ((uint64_t)ord_of(expr) << 32) | 0xffffffffull;
-      const uint64_t l = lat_select(spill, nspill, want, lim, hist);
-      if (l == 0ull) {  // nothing within the radius: the search ends
-        nspill = 0;
-        T = ~0ull;
-        return;
-      }
-      uint32_t out = 0;
-      for (uint32_t b0 = 0; b0 < nspill; b0 += 64) {
-        const uint32_t i = b0 + (uint32_t)lane;
-        const uint64_t key = i < nspill ? spill[i] : ~0ull;
-        const bool in = i < nspill && key <= lim;
-        const bool mv = in && key < l;
-        const bool sy = in && !mv;
-        const uint64_t mm = ballot64(mv), sm = ballot64(sy);
-        __builtin_amdgcn_wave_barrier();
-        if (mv) tail[ntail + mbcnt(mm)] = key;
-        if (sy) spill[out + mbcnt(sm)] = key;
-        __builtin_amdgcn_wave_barrier();
-        ntail += (uint32_t)__popcll(mm);
-        out += (uint32_t)__popcll(sm);
-      }
-      nspill = out;
-      T = nspill ? l : ~0ull;
-      if ((ntail == 0u || ntail > want) && lane == 0) atomicOr(a.error, 64);  // selection check
-    };
-    // an empty head takes the (at most 64) smallest tail keys, sorted across
-    // the lanes by a bitonic network
-    auto refill_head = [&]() {
-      if (ntail == 0 && nspill != 0) refill_tail();
-      if (ntail == 0) return;
-      const uint64_t t = lat_select(tail, ntail, 64u, ~0ull, hist);
-      uint64_t* st64 = reinterpret_cast<uint64_t*>(hist + 64);  // 64 staged keys
-      uint32_t got = 0, out = 0;
-      for (uint32_t b0 = 0; b0 < ntail; b0 += 64) {
-        const uint32_t i = b0 + (uint32_t)lane;
-        const uint64_t key = i < ntail ? tail[i] : ~0ull;
-        const bool mv = i < ntail && key < t;
-        const bool kp = i < ntail && !mv;
-        const uint64_t mm = ballot64(mv), km = ballot64(kp);
-        __builtin_amdgcn_wave_barrier();
-        if (mv) st64[got + mbcnt(mm)] = key;
-        if (kp) tail[out + mbcnt(km)] = key;
-        __builtin_amdgcn_wave_barrier();
-        got += (uint32_t)__popcll(mm);
-        out += (uint32_t)__popcll(km);
-      }
-      uint64_t v = (uint32_t)lane < got ? st64[lane] : ~0ull;
-      ntail = out;
-      if ((got == 0u || got > 64u) && lane == 0) atomicOr(a.error, 128);  // selection check
-#pragma unroll
-      for (int kk = 2; kk <= 64; kk <<= 1) {
-#pragma unroll
-        for (int j = kk >> 1; j > 0; j >>= 1) {
-          const uint64_t o = shfl_xor_u64(v, j);
-          const bool up = ((lane & kk) == 0);
-          const bool lower = (lane & j) == 0;
-          const uint64_t mn = o < v ? o : v, mx = o < v ? v : o;
-          v = (lower == up) ? mn : mx;
-        }
-      }
-      hk = v;
-      hn = got;
-      B = (ntail + nspill) ? readlane_u64(hk, (int)got - 1) + 1 : ~0ull;
-      __builtin_amdgcn_wave_barrier();
-    };
-    auto pop = [&](uint64_t& key) -> bool {
-      if (hn == 0) refill_head();
-      if (hn == 0) return false;
-      key = readlane_u64(hk, 0);
-      const uint64_t dk = wave_down1_u64(hk);
-      hk = (uint32_t)lane < hn - 1 ? dk : ~0ull;
-      hn--;
-      return true;
-    };
+    // ---- the unchecked set (unchecked_set.h), its tail in st.cq: a pop is a
+    // lane shift and never scans anything, where the chunk-minimum scans of a
+    // flat spill were most of an expansion's time on a large quantized graph.
+    // Its spill trims are counter 7.
+    UncheckedSet<false, true> us(st.cq, a.cq_cap, spill, a.spill_cap, hist, reinterpret_cast<uint64_t*>(hist + 64),
+                                 expr);
 
     // ---- setupDistances (exact L2) + setupSeeds (Graph.cpp:293-367) -------
     const uint64_t sb = a.seed_off ? a.seed_off[qi] : (uint64_t)qi * a.seed_stride;
@@ -1164,7 +969,7 @@ __global__ void __launch_bounds__(64, NGT_AMD_QG_WPE) ngt_qg_search_kernel(QgSea
       for (uint32_t j = 0; j < m; j++) {
         const float d = st.nd[j];
         const uint32_t id = st.nid[j];
-        insert_key(make_key(d, packed ? a.qkw[id] : id));
+        us.insert(make_key(d, packed ? a.qkw[id] : id));
         if (d <= a.radius) res_insert(st.res, nres, size, make_key(d, id));
       }
       nexact += m;
@@ -1185,7 +990,7 @@ __global__ void __launch_bounds__(64, NGT_AMD_QG_WPE) ngt_qg_search_kernel(QgSea
 #endif
     for (;;) {
       uint64_t wbest;
-      if (!pop(wbest)) break;
+      if (!us.pop(wbest)) break;
       if (key_dist(wbest) > expr) break;
       nexp++;
       NGT_MARK(t_pop);
@@ -1242,7 +1047,7 @@ __global__ void __launch_bounds__(64, NGT_AMD_QG_WPE) ngt_qg_search_kernel(QgSea
           // results by (distance, id); the unchecked set by (distance, key
           // word) in the packed layout -- the same order
           const uint64_t rkey = make_key(d, st.nid[base + j]);
-          insert_key(packed ? make_key(d, nkw[base + j]) : rkey);
+          us.insert(packed ? make_key(d, nkw[base + j]) : rkey);
           if (d <= radius) {
             res_insert(st.res, nres, size, rkey);
             if (nres >= size) {
@@ -1303,6 +1108,7 @@ __global__ void __launch_bounds__(64, NGT_AMD_QG_WPE) ngt_qg_search_kernel(QgSea
     }
     if (lane == 0) {
       a.out_n[qi] = nout;
+      if (us.err) atomicOr(a.error, (int)us.err);
       if (a.counters) {
         uint64_t* c = a.counters + (uint64_t)qi * 8;
         c[0] = nadc;
@@ -1310,9 +1116,9 @@ __global__ void __launch_bounds__(64, NGT_AMD_QG_WPE) ngt_qg_search_kernel(QgSea
         c[2] = nexp;
         c[3] = nexact;
         c[4] = nblk;
-        c[5] = maxq;
+        c[5] = us.maxq;
         c[6] = (bitmap_mode && use_hash) ? 1 : 0;
-        c[7] = ntrim;
+        c[7] = us.ntrim;
 #ifdef NGT_AMD_STAMPS
         c[4] = t_pop;
         c[5] = t_ids;

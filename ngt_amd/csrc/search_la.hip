@@ -38,6 +38,7 @@
 #include "ngt_kernels.h"
 #include "search_common.h"
 #include "search_layout.h"
+#include "unchecked_set.h"
 
 namespace ngt_amd {
 
@@ -66,13 +67,6 @@ __device__ __forceinline__ void vf_set(uint32_t* vf, uint32_t shift, uint32_t id
 __device__ __forceinline__ bool vf_test(const uint32_t* vf, uint32_t shift, uint32_t id) {
   const uint32_t b = (id * 0x85EBCA77u) >> shift;
   return (vf[b >> 5] >> (b & 31)) & 1u;
-}
-
-// a wave-uniform u64 in SGPRs (the reductions leave it in every lane)
-__device__ __forceinline__ uint64_t uniform_u64(uint64_t v) {
-  const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
-  const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32));
-  return ((uint64_t)hi << 32) | lo;
 }
 
 // WPE: resident waves per SIMD the kernel is compiled for (VGPR budget)
@@ -165,20 +159,13 @@ ngt_graph_search_la_kernel(SearchArgs a) {
     float radius = a.radius;
     float expr = 0.f;
     double frq = 0.0;
-    // ---- the unchecked set: three levels with key thresholds B and T -------
-    // head (wave 0's registers, sorted: lane i = i-th smallest, hn keys) < B
-    // <= tail (LDS, unsorted, ncq keys) < T <= spill (HBM, per slot), so the
-    // smallest keys are always in the head while it is non-empty: a step's
-    // targets are its first lanes and a pop is a lane shift.  A full head
-    // sends its largest key to the tail (B drops); an emptying head takes the
-    // smallest tail keys (histogram threshold + bitonic sort, B rises).  A full
-    // tail is compacted (keys beyond the exploration radius can never be
-    // popped, Graph.cpp:433-435) and, if still over half full, its larger half
-    // moves to the spill (T drops); an empty tail refills with the smallest
-    // spill keys (T rises).  Exact throughout.
-    uint64_t hk = ~0ull, B = ~0ull;
-    uint32_t hn = 0;
-    uint64_t T = ~0ull;
+    // ---- the unchecked set: the three levels of unchecked_set.h (head in
+    // wave 0's registers, tail in cq, spill per slot) with this kernel's own
+    // policies: a step's targets are the head's first lanes, so the head is
+    // topped up while it holds fewer than P keys, not refilled when empty;
+    // make_room bisects for its threshold and refill uses a width histogram.
+    SortedHead<false> head;
+    uint64_t B = ~0ull, T = ~0ull;
     auto spill_push = [&](uint64_t key) {
       if (nspill >= a.spill_cap) {
         if (lane == 0) atomicOr(a.error, 1);
@@ -192,29 +179,20 @@ ngt_graph_search_la_kernel(SearchArgs a) {
     };
     // move the LDS keys >= t to the spill (t lowers T)
     auto lds_to_spill = [&](uint64_t t) {
-      uint32_t out = 0;
-      for (uint32_t b = 0; b < ncq; b += 64) {
-        const uint32_t i = b + (uint32_t)lane;
-        const uint64_t key = i < ncq ? cq[i] : ~0ull;
-        const bool mv = i < ncq && key >= t;
-        const bool keep = i < ncq && key < t;
-        const uint64_t mm = ballot64(mv), km = ballot64(keep);
-        const uint32_t nm = (uint32_t)__popcll(mm);
-        if (nspill + nm > a.spill_cap) {
-          if (lane == 0) atomicOr(a.error, 1);
-        } else if (mv) {
-          spill[nspill + mbcnt(mm)] = key;
-        }
-        if (nspill + nm <= a.spill_cap) nspill += nm;
+      ncq = partition_keys(cq, ncq, [&](uint64_t key) { return key < t; },
+                           [&](uint64_t key, bool mv) {
+                             const uint64_t mm = ballot64(mv);
+                             const uint32_t nm = (uint32_t)__popcll(mm);
+                             if (nspill + nm > a.spill_cap) {
+                               if (lane == 0) atomicOr(a.error, 1);
+                             } else {
+                               if (mv) spill[nspill + mbcnt(mm)] = key;
+                               nspill += nm;
+                             }
 #ifdef NGT_AMD_LACOUNT
-        n_spw += nm;
+                             n_spw += nm;
 #endif
-        __builtin_amdgcn_wave_barrier();
-        if (keep) cq[out + mbcnt(km)] = key;
-        __builtin_amdgcn_wave_barrier();
-        out += (uint32_t)__popcll(km);
-      }
-      ncq = out;
+                           });
       T = t;
     };
     auto make_room = [&]() {
@@ -353,29 +331,24 @@ ngt_graph_search_la_kernel(SearchArgs a) {
     };
     auto insert_key = [&](uint64_t key) {
       if (key < B) {
-        const uint32_t pos = (uint32_t)__popcll(ballot64((uint32_t)lane < hn && hk < key));
-        const uint64_t uk = wave_up1_u64(hk);
-        if (hn == 64u) {
-          // the head is full: its largest key (or this one) moves to the tail
-          if (pos == 64u) {
-            B = key;
-            tail_insert(key);
-          } else {
-            const uint64_t e = readlane_u64(hk, 63);
-            if ((uint32_t)lane > pos) hk = uk;
-            if ((uint32_t)lane == pos) hk = key;
-            B = e;
-            tail_insert(e);
-          }
+        const uint32_t pos = head.rank(key);
+        if (pos == 64u) {
+          // beyond a full head: straight to the tail
+          B = key;
+          tail_insert(key);
+        } else if (head.hn == 64u) {
+          // the head is full: its largest key moves to the tail
+          const uint64_t e = readlane_u64(head.hk, 63);
+          head.insert_at(pos, key);
+          B = e;
+          tail_insert(e);
         } else {
-          if ((uint32_t)lane > pos && (uint32_t)lane <= hn) hk = uk;
-          if ((uint32_t)lane == pos) hk = key;
-          hn++;
+          head.insert_at(pos, key);
         }
       } else {
         tail_insert(key);
       }
-      if (hn + ncq + nspill > maxq) maxq = hn + ncq + nspill;
+      if (head.hn + ncq + nspill > maxq) maxq = head.hn + ncq + nspill;
     };
     // fill the head up with the smallest tail keys (the tail takes the
     // smallest spill keys first when it is empty): at most 64 - hn keys, all
@@ -383,51 +356,26 @@ ngt_graph_search_la_kernel(SearchArgs a) {
     auto refill_head = [&]() {
       if (ncq == 0 && nspill != 0) refill();
       if (ncq == 0) return;
-      const uint32_t room = 64u - hn;
+      const uint32_t room = 64u - head.hn;
       const uint64_t t = lat_select(cq, ncq, room, ~0ull, nid);
       uint64_t* st64 = reinterpret_cast<uint64_t*>(nid);  // 64 x u64 staged through nid/nd (adjacent)
-      uint32_t got = 0, out = 0;
-      for (uint32_t b0 = 0; b0 < ncq; b0 += 64) {
-        const uint32_t i = b0 + (uint32_t)lane;
-        const uint64_t key = i < ncq ? cq[i] : ~0ull;
-        const bool mv = i < ncq && key < t;
-        const bool kp = i < ncq && !mv;
-        const uint64_t mm = ballot64(mv), km = ballot64(kp);
-        __builtin_amdgcn_wave_barrier();
-        if (mv && got + mbcnt(mm) < room) st64[got + mbcnt(mm)] = key;
-        if (kp) cq[out + mbcnt(km)] = key;
-        __builtin_amdgcn_wave_barrier();
-        got += (uint32_t)__popcll(mm);
-        out += (uint32_t)__popcll(km);
-      }
+      uint32_t got = 0;
+      ncq = partition_keys(cq, ncq, [&](uint64_t key) { return key >= t; },
+                           [&](uint64_t key, bool mv) {
+                             const uint64_t mm = ballot64(mv);
+                             if (mv && got + mbcnt(mm) < room) st64[got + mbcnt(mm)] = key;
+                             got += (uint32_t)__popcll(mm);
+                           });
       if (got == 0u || got > room) {
         if (lane == 0) atomicOr(a.error, 8);  // selection check: never expected
         got = got > room ? room : got;
       }
-      ncq = out;
-      uint64_t v = (uint32_t)lane < hn ? hk : ((uint32_t)lane < hn + got ? st64[lane - hn] : ~0ull);
+      const uint64_t v = (uint32_t)lane < head.hn ? head.hk
+                                                  : ((uint32_t)lane < head.hn + got ? st64[lane - head.hn] : ~0ull);
       __builtin_amdgcn_wave_barrier();
-      // bitonic sort of the 64 lanes (ascending; empty lanes hold ~0)
-#pragma unroll
-      for (int kk = 2; kk <= 64; kk <<= 1) {
-#pragma unroll
-        for (int j = kk >> 1; j > 0; j >>= 1) {
-          const uint64_t o = shfl_xor_u64(v, j);
-          const bool up = ((lane & kk) == 0);
-          const bool lower = (lane & j) == 0;
-          const uint64_t mn = o < v ? o : v, mx = o < v ? v : o;
-          v = (lower == up) ? mn : mx;
-        }
-      }
-      hk = v;
-      hn += got;
-      B = (ncq + nspill) ? readlane_u64(hk, (int)hn - 1) + 1 : ~0ull;
-    };
-    // the head's first key leaves (the commit of a target)
-    auto pop_head = [&]() {
-      const uint64_t dk = wave_down1_u64(hk);
-      hk = (uint32_t)lane + 1 < hn ? dk : ~0ull;
-      hn--;
+      head.hk = bitonic_sort64(v);
+      head.hn += got;
+      B = (ncq + nspill) ? readlane_u64(head.hk, (int)head.hn - 1) + 1 : ~0ull;
     };
     // keys entering the unchecked set during the commit of target cur_j: the
     // first later target they precede can no longer be the reference's next
@@ -490,7 +438,7 @@ ngt_graph_search_la_kernel(SearchArgs a) {
             tail_insert(readlane_u64(key, j));
           }
         }
-        if (hn + ncq + nspill > maxq) maxq = hn + ncq + nspill;
+        if (head.hn + ncq + nspill > maxq) maxq = head.hn + ncq + nspill;
       }
     };
     // wave 0: accept the evaluated neighbours of the lanes in km (lane order
@@ -588,11 +536,11 @@ ngt_graph_search_la_kernel(SearchArgs a) {
       // when it holds fewer than P keys).  They stay in the head; each
       // committed target leaves it at its commit (phase F).
       if (wave == 0) {
-        if (hn < (uint32_t)P && (ncq | nspill) != 0u) refill_head();
-        const uint32_t lim = hn < (uint32_t)P ? hn : (uint32_t)P;
-        const uint32_t nt = (uint32_t)__popcll(ballot64((uint32_t)lane < lim && key_dist(hk) <= expr));
+        if (head.hn < (uint32_t)P && (ncq | nspill) != 0u) refill_head();
+        const uint32_t lim = head.hn < (uint32_t)P ? head.hn : (uint32_t)P;
+        const uint32_t nt = (uint32_t)__popcll(ballot64((uint32_t)lane < lim && key_dist(head.hk) <= expr));
 #pragma unroll
-        for (int j = 0; j < P; j++) tk[j] = (uint32_t)j < nt ? readlane_u64(hk, j) : ~0ull;
+        for (int j = 0; j < P; j++) tk[j] = (uint32_t)j < nt ? readlane_u64(head.hk, j) : ~0ull;
         const uint32_t done = nt == 0 ? 1u : 0u;  // empty, or the minimum is beyond the radius (Graph.cpp:433-435)
         if (lane == 0) {
 #pragma unroll
@@ -889,8 +837,8 @@ ngt_graph_search_la_kernel(SearchArgs a) {
           }
           // t_j is the head's first key here: t_0..t_{j-1} left it and no
           // key pushed since precedes t_j (nblock > j)
-          if (readlane_u64(hk, 0) != tk_at(j) && lane == 0) atomicOr(a.error, 8);
-          pop_head();
+          if (readlane_u64(head.hk, 0) != tk_at(j) && lane == 0) atomicOr(a.error, 8);
+          head.pop_first();
           ncommit++;
           nexp++;
           const uint32_t lb = loff[j], le = loff[j + 1];

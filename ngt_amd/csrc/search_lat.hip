@@ -34,12 +34,12 @@
 #include "ngt_kernels.h"
 #include "search_common.h"
 #include "search_layout.h"
+#include "unchecked_set.h"
 
 namespace ngt_amd {
 
 namespace {
 
-constexpr uint32_t kNoTag = 0xffu;  // head entry without a slot
 constexpr uint32_t kFree = 0u, kIssued = 1u;
 
 __device__ __forceinline__ bool bm_test(const uint32_t* bm, uint32_t id) { return (bm[id >> 5] >> (id & 31)) & 1u; }
@@ -295,7 +295,7 @@ __global__ void __launch_bounds__(64 * W) ngt_graph_search_lat_kernel(SearchArgs
 
     if (wave == 0) {
       // =================== the commit wave ===================================
-      uint32_t nres = 0, maxq = 0;
+      uint32_t nres = 0;
       // the result set (Graph.cpp:471-483's ResultSet, k <= 64) in registers:
       // lane i holds the i-th smallest (distance, id) key
       uint64_t rk = ~0ull;
@@ -319,213 +319,16 @@ __global__ void __launch_bounds__(64 * W) ngt_graph_search_lat_kernel(SearchArgs
         expr = __fmul_rn(coefq, radius);
         if (lane == 0) __hip_atomic_store(&ctl->expr, expr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
       };
-      // unchecked set: head (registers, sorted, hn keys) < B <= tail (LDS,
-      // ntail keys) < T <= spill (HBM, nspill keys)
-      uint64_t hk = ~0ull;
-      uint32_t ht = kNoTag;
-      uint32_t hn = 0, ntail = 0, nspill = 0;
-      uint64_t B = ~0ull, T = ~0ull;
+      // the unchecked set (unchecked_set.h): a head entry's tag is the slot
+      // that speculates it, us.orphan the issued slots whose entry left the
+      // head (freed once their speculation is done); the 64 keys on their way
+      // into the head are staged through nid/nd (adjacent 256 B each)
+      UncheckedSet<true, false> us(tail, a.lat_tail, spill, a.spill_cap, hist, reinterpret_cast<uint64_t*>(nid), expr);
       uint64_t freem = nslots >= 64 ? ~0ull : ((1ull << nslots) - 1ull);  // free slots
       uint32_t sgen = 0u;  // lane s: slot s's issue generation (only this wave issues)
-      uint64_t orphan = 0ull;                                             // issued, no longer in the head
       const uint32_t Fd = a.lat_feed ? a.lat_feed : 16u;
       const uint32_t F = nslots < Fd ? nslots : Fd;                       // head entries kept speculated
 
-      auto spill_push = [&](uint64_t key) {
-        if (nspill >= a.spill_cap) {
-          qerr |= 1u;
-        } else {
-          if (lane == 0) spill[nspill] = key;
-          nspill++;
-        }
-      };
-      auto select_t = [&](const uint64_t* arr, uint32_t n, uint32_t M, uint64_t lim) -> uint64_t {
-        return lat_select(arr, n, M, lim, hist);
-      };
-      // the tail is full: drop keys beyond the exploration radius (never
-      // popped, Graph.cpp:433-435); if still over half full, move the keys
-      // from a threshold up to the spill (T drops)
-      auto tail_room = [&]() {
-        uint32_t out = 0;
-        for (uint32_t b0 = 0; b0 < ntail; b0 += 64) {
-          const uint32_t i = b0 + (uint32_t)lane;
-          const uint64_t key = i < ntail ? tail[i] : ~0ull;
-          const bool keep = i < ntail && key_dist(key) <= expr;
-          const uint64_t km = ballot64(keep);
-          __builtin_amdgcn_wave_barrier();
-          if (keep) tail[out + mbcnt(km)] = key;
-          __builtin_amdgcn_wave_barrier();
-          out += (uint32_t)__popcll(km);
-        }
-        ntail = out;
-        const uint32_t keep = a.lat_tail / 2;
-        if (ntail <= keep) return;
-        const uint64_t l = select_t(tail, ntail, keep, ~0ull);
-        out = 0;
-        for (uint32_t b0 = 0; b0 < ntail; b0 += 64) {
-          const uint32_t i = b0 + (uint32_t)lane;
-          const uint64_t key = i < ntail ? tail[i] : ~0ull;
-          const bool mv = i < ntail && key >= l;
-          const bool kp = i < ntail && key < l;
-          const uint64_t mm = ballot64(mv), km = ballot64(kp);
-          const uint32_t nm = (uint32_t)__popcll(mm);
-          if (nspill + nm > a.spill_cap) {
-            qerr |= 1u;
-          } else if (mv) {
-            spill[nspill + mbcnt(mm)] = key;
-          }
-          if (nspill + nm <= a.spill_cap) nspill += nm;
-          __builtin_amdgcn_wave_barrier();
-          if (kp) tail[out + mbcnt(km)] = key;
-          __builtin_amdgcn_wave_barrier();
-          out += (uint32_t)__popcll(km);
-        }
-        if (out == 0u || out > keep) qerr |= 32u;  // selection check
-        ntail = out;
-        T = l;
-      };
-      auto tail_push = [&](uint64_t key) {
-        if (key >= T) {
-          spill_push(key);
-        } else {
-          if (ntail >= a.lat_tail) tail_room();
-          if (key >= T) {
-            spill_push(key);
-          } else {
-            if (lane == 0) tail[ntail] = key;
-            ntail++;
-          }
-        }
-        __builtin_amdgcn_wave_barrier();
-      };
-      // an issued head entry leaving the head: its slot is freed once ready
-      auto orphan_tag = [&](uint32_t tag) {
-        if (tag != kNoTag) orphan |= 1ull << tag;
-      };
-      auto insert_key = [&](uint64_t key) {
-        if (key < B) {
-          const uint32_t pos = (uint32_t)__popcll(ballot64((uint32_t)lane < hn && hk < key));
-          if (hn == 64u) {
-            // the head is full: its largest key (or this one) moves to the tail
-            if (pos == 64u) {
-              B = key;
-              tail_push(key);
-              return;
-            }
-            const uint64_t e = readlane_u64(hk, 63);
-            orphan_tag((uint32_t)__builtin_amdgcn_readlane((int)ht, 63));
-            const uint64_t uk = wave_up1_u64(hk);
-            const uint32_t ut = wave_up1(ht);
-            if ((uint32_t)lane > pos) { hk = uk; ht = ut; }
-            if ((uint32_t)lane == pos) { hk = key; ht = kNoTag; }
-            B = e;
-            tail_push(e);
-          } else {
-            const uint64_t uk = wave_up1_u64(hk);
-            const uint32_t ut = wave_up1(ht);
-            if ((uint32_t)lane > pos && (uint32_t)lane <= hn) { hk = uk; ht = ut; }
-            if ((uint32_t)lane == pos) { hk = key; ht = kNoTag; }
-            hn++;
-          }
-        } else {
-          tail_push(key);
-        }
-        const uint32_t q = hn + ntail + nspill;
-        if (q > maxq) maxq = q;
-      };
-      // an empty head takes the smallest keys of the tail (the tail the
-      // smallest of the spill first): a histogram threshold that moves 32..64
-      // keys, then a bitonic sort across the lanes
-      auto refill_tail = [&]() {
-        // nothing in LDS: the smallest spill keys within the radius move in,
-        // the ones beyond it are dropped
-        const uint32_t want = a.lat_tail / 2;
-        const uint64_t lim = ((uint64_t)ord_of(expr) << 32) | 0xffffffffull;
-        const uint64_t l = select_t(spill, nspill, want, lim);
-        if (l == 0ull) {  // nothing within the radius: the search ends
-          nspill = 0;
-          T = ~0ull;
-          return;
-        }
-        uint32_t out = 0;
-        for (uint32_t b0 = 0; b0 < nspill; b0 += 64) {
-          const uint32_t i = b0 + (uint32_t)lane;
-          const uint64_t key = i < nspill ? spill[i] : ~0ull;
-          const bool in = i < nspill && key <= lim;
-          const bool mv = in && key < l;
-          const bool st = in && !mv;
-          const uint64_t mm = ballot64(mv), sm = ballot64(st);
-          __builtin_amdgcn_wave_barrier();
-          if (mv) tail[ntail + mbcnt(mm)] = key;
-          if (st) spill[out + mbcnt(sm)] = key;
-          __builtin_amdgcn_wave_barrier();
-          ntail += (uint32_t)__popcll(mm);
-          out += (uint32_t)__popcll(sm);
-        }
-        nspill = out;
-        T = nspill ? l : ~0ull;
-        if (ntail == 0u || ntail > want) qerr |= 64u;  // selection check
-      };
-      auto refill_head = [&]() {
-        if (ntail == 0 && nspill != 0) refill_tail();
-        if (ntail == 0) return;
-        // the (at most 64, at least 32 when there are) smallest tail keys
-        const uint64_t t = select_t(tail, ntail, 64u, ~0ull);
-        // move tail keys < t into the head lanes (unsorted), compact the tail
-        uint64_t v = ~0ull;
-        uint32_t got = 0, out = 0;
-        for (uint32_t b0 = 0; b0 < ntail; b0 += 64) {
-          const uint32_t i = b0 + (uint32_t)lane;
-          const uint64_t key = i < ntail ? tail[i] : ~0ull;
-          const bool mv = i < ntail && key < t;
-          const bool kp = i < ntail && !mv;
-          const uint64_t mm = ballot64(mv), km = ballot64(kp);
-          // lane (got + rank) of the head receives the key
-          const uint32_t dst = got + mbcnt(mm);
-          uint32_t* stage = nid;  // 64 x u64 staged through nid/nd (adjacent 256 B each)
-          uint64_t* st64 = reinterpret_cast<uint64_t*>(stage);
-          __builtin_amdgcn_wave_barrier();
-          if (mv) st64[dst] = key;
-          if (kp) tail[out + mbcnt(km)] = key;
-          __builtin_amdgcn_wave_barrier();
-          got += (uint32_t)__popcll(mm);
-          out += (uint32_t)__popcll(km);
-        }
-        {
-          const uint64_t* st64 = reinterpret_cast<const uint64_t*>(nid);
-          v = (uint32_t)lane < got ? st64[lane] : ~0ull;
-        }
-        ntail = out;
-        if (got == 0u || got > 64u) qerr |= 128u;  // selection check
-        // bitonic sort of the 64 lanes (ascending; empty lanes hold ~0)
-#pragma unroll
-        for (int kk = 2; kk <= 64; kk <<= 1) {
-#pragma unroll
-          for (int j = kk >> 1; j > 0; j >>= 1) {
-            const uint64_t o = shfl_xor_u64(v, j);
-            const bool up = ((lane & kk) == 0);
-            const bool lower = (lane & j) == 0;
-            const uint64_t mn = o < v ? o : v, mx = o < v ? v : o;
-            v = (lower == up) ? mn : mx;
-          }
-        }
-        hk = v;
-        ht = kNoTag;
-        hn = got;
-        B = (ntail + nspill) ? readlane_u64(hk, (int)got - 1) + 1 : ~0ull;
-      };
-      auto pop = [&](uint64_t& key, uint32_t& tag) -> bool {
-        if (hn == 0) refill_head();
-        if (hn == 0) return false;
-        key = readlane_u64(hk, 0);
-        tag = (uint32_t)__builtin_amdgcn_readlane((int)ht, 0);
-        const uint64_t dk = wave_down1_u64(hk);
-        const uint32_t dt = wave_down1(ht);
-        hk = (uint32_t)lane < hn - 1 ? dk : ~0ull;
-        ht = (uint32_t)lane < hn - 1 ? dt : kNoTag;
-        hn--;
-        return true;
-      };
       // a slot the commit wave is done with goes back to freem
       auto release_slot = [&](uint32_t t) {
         if (lane == 0) slots[t].state = kFree;
@@ -533,13 +336,13 @@ __global__ void __launch_bounds__(64 * W) ngt_graph_search_lat_kernel(SearchArgs
       };
       // free the orphaned slots whose speculation has finished
       auto reap = [&]() {
-        uint64_t o = orphan;
+        uint64_t o = us.orphan;
         while (o) {
           const int s = __ffsll((long long)o) - 1;
           o &= o - 1;
           if (lds_load_acq(&slots[s].pready) == pfull) {
             release_slot((uint32_t)s);
-            orphan &= ~(1ull << s);
+            us.orphan &= ~(1ull << s);
           }
         }
       };
@@ -549,19 +352,19 @@ __global__ void __launch_bounds__(64 * W) ngt_graph_search_lat_kernel(SearchArgs
       // expected) flags error 16 and ends the query instead of hanging the CU
       bool stuck = false;
       auto issue = [&](uint64_t key) -> uint32_t {
-        if (freem == 0ull && orphan == 0ull) {
+        if (freem == 0ull && us.orphan == 0ull) {
           // every slot is held by a head entry (tagged entries pushed past the
           // first F lanes by smaller accepted keys, then F more tagged), and
           // the node to expand has none: nothing comes back to freem by
           // itself, so the deepest tagged head entry gives its slot up
           // (orphaned, freed once its speculation is done; the entry is
           // issued again when it nears the front)
-          const uint64_t om = ballot64(ht < nslots);
+          const uint64_t om = ballot64(us.ht < nslots);
           if (om != 0ull) {
             const int l = 63 - __builtin_clzll(om);
-            const uint32_t t = (uint32_t)__builtin_amdgcn_readlane((int)ht, l);
-            if (lane == l) ht = kNoTag;
-            orphan |= 1ull << t;
+            const uint32_t t = (uint32_t)__builtin_amdgcn_readlane((int)us.ht, l);
+            if (lane == l) us.ht = kNoTag;
+            us.orphan |= 1ull << t;
           }
         }
         for (uint32_t spin = 0; freem == 0ull; spin++) {
@@ -596,16 +399,16 @@ __global__ void __launch_bounds__(64 * W) ngt_graph_search_lat_kernel(SearchArgs
       };
       // speculation for the first F head entries that have none
       auto feed = [&]() {
-        if (orphan) reap();
-        uint64_t need = ballot64((uint32_t)lane < (hn < F ? hn : F) && ht == kNoTag);
+        if (us.orphan) reap();
+        uint64_t need = ballot64((uint32_t)lane < (us.hn < F ? us.hn : F) && us.ht == kNoTag);
         while (need) {
           const int l = __ffsll((long long)need) - 1;
           need &= need - 1;
-          const uint64_t key = readlane_u64(hk, l);
+          const uint64_t key = readlane_u64(us.hk, l);
           if (freem == 0ull) break;
           const uint32_t s = issue(key);
           if (stuck) break;
-          if (lane == l) ht = s;
+          if (lane == l) us.ht = s;
         }
       };
       // accept the candidates held in registers in neighbour order
@@ -617,7 +420,7 @@ __global__ void __launch_bounds__(64 * W) ngt_graph_search_lat_kernel(SearchArgs
           while (m) {
             const int j = __ffsll((long long)m) - 1;
             m &= m - 1;
-            insert_key(make_key(__int_as_float(__builtin_amdgcn_readlane(__float_as_int(dv), j)),
+            us.insert(make_key(__int_as_float(__builtin_amdgcn_readlane(__float_as_int(dv), j)),
                                 (uint32_t)__builtin_amdgcn_readlane((int)idv, j)));
           }
         };
@@ -632,7 +435,7 @@ __global__ void __launch_bounds__(64 * W) ngt_graph_search_lat_kernel(SearchArgs
           push(okmask & ((1ull << j) - 1ull));
           const uint64_t key = make_key(__int_as_float(__builtin_amdgcn_readlane(__float_as_int(dv), j)),
                                         (uint32_t)__builtin_amdgcn_readlane((int)idv, j));
-          insert_key(key);
+          us.insert(key);
           res_push(key);
           if (nres >= k) {
             radius = key_dist(readlane_u64(rk, (int)k - 1));
@@ -672,7 +475,7 @@ __global__ void __launch_bounds__(64 * W) ngt_graph_search_lat_kernel(SearchArgs
         for (uint32_t j = 0; j < m; j++) {
           const float d = nd[j];
           const uint64_t key = make_key(d, nid[j]);
-          insert_key(key);
+          us.insert(key);
           if (d <= radq) res_push(key);
         }
         __builtin_amdgcn_wave_barrier();
@@ -689,7 +492,7 @@ __global__ void __launch_bounds__(64 * W) ngt_graph_search_lat_kernel(SearchArgs
       for (;;) {
         uint64_t key;
         uint32_t tag;
-        if (!pop(key, tag)) break;
+        if (!us.pop(key, tag)) break;
         if (key_dist(key) > expr) break;  // Graph.cpp:433-435
         if (tag == kNoTag) {
           tag = issue(key);
@@ -770,7 +573,8 @@ __global__ void __launch_bounds__(64 * W) ngt_graph_search_lat_kernel(SearchArgs
       if (lane == 0) lds_store_rel(&ctl->done, 1u);
 
       // ---- results (moveFrom: ascending (distance, id), ObjectSpace.h:49-57)
-      uint64_t cv[8] = {ndist, ndist - ns, nexp, nstall, nedge, maxq, nexact, ns};
+      qerr |= us.err;
+      uint64_t cv[8] = {ndist, ndist - ns, nexp, nstall, nedge, us.maxq, nexact, ns};
 #ifdef NGT_AMD_STAMPS
       // phase cycles: [5] pop (+ refills, issue), [6] waits for list parts,
       // [1] list reads + visited test and mark, [3] accepts, [7] feeding the
