@@ -1077,8 +1077,8 @@ static int linear_search_mfma(ngt_amd_index* ix, SearchCtx* c, LinearArgs& a, hi
     LinearArgs ac = a;
     ac.nq = nqc;
     ac.partial = m.partial;
-    ac.out_ids = a.out_ids + (size_t)mb0 * 128 * a.k;
-    ac.out_dists = a.out_dists + (size_t)mb0 * 128 * a.k;
+    ac.out_ids = a.out_ids + (size_t)mb0 * 128 * a.out_stride;
+    ac.out_dists = a.out_dists + (size_t)mb0 * 128 * a.out_stride;
     ac.out_n = a.out_n + (size_t)mb0 * 128;
     HIP_OK(launch_linear_merge(ac, nparts, s));
     poff += (size_t)nqc * nparts * a.k;
@@ -1114,7 +1114,11 @@ extern "C" int ngt_amd_linear_search_device(ngt_amd_index* ix, const void* d_que
   a.queries = static_cast<const uint8_t*>(d_queries);
   a.query_bytes = query_bytes;
   a.nq = nq;
-  a.k = k;
+  // linearSearch returns min(k, live rows) results (ObjectSpaceRepository.h:466-502):
+  // lists no longer than the table hold them all; the outputs keep the stride k
+  a.k = (uint32_t)std::min<uint64_t>(k, std::max<uint64_t>(ix->nrows, 2) - 1);
+  a.out_stride = k;
+  k = a.k;
   a.radius = radius;
   a.out_ids = d_ids;
   a.out_dists = d_dists;
@@ -1153,6 +1157,13 @@ extern "C" int ngt_amd_linear_search_device(ngt_amd_index* ix, const void* d_que
     if (e != hipErrorNotSupported) return fail("ngt_amd_linear_search_device: scan launch failed: %s",
                                                hipGetErrorString(e));
   }
+  // the quad-per-row kernel keeps its k-list in LDS
+  if (linear_search_lds_bytes(k, (int)ix->dp, ix->otype) > kLinearSearchLdsLimit)
+    return fail("ngt_amd_linear_search_device: %u results per query need %llu bytes of LDS, the limit is %llu "
+                "(k <= %llu at this row size; lists are never longer than the table)",
+                k, (unsigned long long)linear_search_lds_bytes(k, (int)ix->dp, ix->otype),
+                (unsigned long long)kLinearSearchLdsLimit,
+                (unsigned long long)((kLinearSearchLdsLimit - linear_search_lds_bytes(0, (int)ix->dp, ix->otype)) / 8 + 1));
   // enough slices to fill the chip: ~4 waves per CU over all queries
   uint64_t want = ((uint64_t)ix->cu_count * 16 + nq - 1) / nq;
   uint64_t maxs = (ix->nrows + 255) / 256;

@@ -227,12 +227,13 @@ struct LinearArgs {
   const uint8_t* queries;
   uint64_t query_bytes;
   uint32_t nq;
-  uint32_t k;
+  uint32_t k;                    // length of the result lists: min(requested, nrows - 1)
   double radius;                 // < 0 => unbounded
   uint64_t* partial;             // [nq][nslices][k]
-  uint32_t* out_ids;
+  uint32_t* out_ids;             // [nq][out_stride]
   float* out_dists;
   uint32_t* out_n;
+  uint32_t out_stride;           // the requested k
 };
 
 struct MergeArgs {
@@ -332,6 +333,9 @@ hipError_t launch_graph_search(const SearchArgs& a, int metric, int otype, uint3
 hipError_t launch_linear_search(const LinearArgs& a, int metric, int otype, uint32_t nslices,
                                 hipStream_t s);
 hipError_t launch_linear_merge(const LinearArgs& a, uint32_t nslices, hipStream_t s);
+// dynamic LDS of ngt_linear_search_kernel: the k-list, a 64-row chunk and the query
+size_t linear_search_lds_bytes(uint32_t k, int dp, int otype);
+constexpr size_t kLinearSearchLdsLimit = 65536;  // what a launch gets without a function attribute
 // query-tiled exact scan (scan_kernels.hip): float L2, Dp <= 256, k <= 32;
 // hipErrorNotSupported otherwise.  Writes a.partial [nq][nparts][k].
 hipError_t launch_linear_scan(const LinearArgs& a, int metric, int otype, uint32_t nparts, uint32_t rows_per_part,

@@ -797,8 +797,8 @@ __global__ void __launch_bounds__(64) ngt_linear_merge_kernel(LinearArgs a, uint
     }
   }
   for (uint32_t i = lane; i < nres; i += 64) {
-    a.out_ids[(uint64_t)qi * a.k + i] = key_id(res[i]);
-    a.out_dists[(uint64_t)qi * a.k + i] = key_dist(res[i]);
+    a.out_ids[(uint64_t)qi * a.out_stride + i] = key_id(res[i]);
+    a.out_dists[(uint64_t)qi * a.out_stride + i] = key_dist(res[i]);
   }
   if (lane == 0) a.out_n[qi] = nres;
 }
@@ -1038,11 +1038,16 @@ hipError_t launch_graph_search(const SearchArgs& a, int metric, int otype, uint3
   return hipGetLastError();
 }
 
+size_t linear_search_lds_bytes(uint32_t k, int dp, int otype) {
+  return (((size_t)8 * ((size_t)k + 1) + 15) & ~(size_t)15) + 512 +
+         (((size_t)dp * (otype == kFloat ? 4 : 1) + 15) & ~(size_t)15);
+}
+
 hipError_t launch_linear_search(const LinearArgs& a, int metric, int otype, uint32_t nslices,
                                 hipStream_t s) {
   if (a.nq == 0) return hipSuccess;
-  const size_t lds = (((size_t)8 * (a.k + 1) + 15) & ~(size_t)15) + 512 +
-                     (((size_t)a.dp * (otype == kFloat ? 4 : 1) + 15) & ~(size_t)15);
+  const size_t lds = linear_search_lds_bytes(a.k, a.dp, otype);
+  if (lds > kLinearSearchLdsLimit) return hipErrorInvalidValue;
 #define L_LIN(MM, TT) hipLaunchKernelGGL((ngt_linear_search_kernel<MM, TT>), dim3(nslices, a.nq), dim3(64), lds, s, a)
   NGT_DISPATCH(metric, otype, L_LIN);
 #undef L_LIN

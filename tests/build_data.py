@@ -110,6 +110,35 @@ def dataset(name, rows=None):
     raise KeyError(name)
 
 
+QUERIES = 32
+STORED_QUERIES = 8  # the first queries of every case equal a stored row
+
+
+def _queries(name):
+    rows, otype = dataset(name)
+    rs = np.random.RandomState(4000 + CASES[name][2] + len(name))
+    pick = rs.permutation(ROWS)[:STORED_QUERIES]
+    fresh = rows[rs.permutation(ROWS)[:QUERIES - STORED_QUERIES]]
+    if otype == "f":
+        fresh = (fresh * np.float32(1.01) + np.float32(0.003)).astype(np.float32)
+    else:
+        fresh = np.clip(fresh + rs.randint(-1, 2, fresh.shape), 0, 255)
+    return np.concatenate([rows[pick], fresh]), pick
+
+
+def queries(name):
+    """The 32 search queries of a 2,000-row case (tests/golden/build_<case>/search.npz,
+    make_search_matrix_goldens.py), as the CLI's text holds them: 8 stored rows,
+    then 24 other rows perturbed -- scaled and shifted floats, uint8 values moved
+    by -1, 0 or 1."""
+    return _queries(name)[0]
+
+
+def stored_query_rows(name):
+    """The 0-based rows the first 8 queries equal."""
+    return _queries(name)[1]
+
+
 def write_text(rows, otype, path):
     """One object per line for `ngt create`: %.9g round-trips float32."""
     with open(path, "w") as f:
