@@ -55,13 +55,8 @@ static int accuracy_table(ngt_amd_index* ix, uint64_t nresults, uint64_t nquerie
 
   std::vector<uint64_t> cnt;
   AccuracySearch search = [&](AccuracyBatch& b) -> std::string {
-    ngt_amd_search_params p{};
-    p.k = (uint32_t)b.size;
-    p.epsilon = b.epsilon;
-    p.radius = -1.0f;  // FLT_MAX
-    p.edge_size = b.edge_size;
-    p.seed_mode = NGT_AMD_SEED_TREE;
-    p.visited_hash_log2 = ix->nrows >= (1u << 18) ? -1 : 0;
+    const ngt_amd_search_params p = library_search_params(ix->nrows, (uint32_t)b.size, b.epsilon, -1.0f /* FLT_MAX */,
+                                                          b.edge_size, NGT_AMD_SEED_TREE);
     cnt.assign((size_t)b.nq * NGT_AMD_COUNTERS_PER_QUERY, 0);
     if (ngt_amd_search(ix, &p, b.queries, b.nq, nullptr, nullptr, b.ids.data(), b.dists.data(), b.n.data(),
                        cnt.data()))

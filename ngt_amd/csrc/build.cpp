@@ -33,6 +33,7 @@
 
 #include "../../include/ngt_amd.h"
 #include "index_internal.h"
+#include "index_io.h"
 #include "ngt_kernels.h"
 #include "remove_kernels.h"
 
@@ -895,4 +896,30 @@ extern "C" int ngt_amd_build_get_tree(const ngt_amd_index* ix, uint32_t* leaf_pa
     leaf_off[i + 1] = e;
   }
   return 0;
+}
+
+int ngt_amd::build_tree_to_host(const ngt_amd_index* ix, uint64_t row_bytes, HostTree& t) {
+  uint32_t nl = 0, ni = 0;
+  uint64_t nli = 0;
+  if (ngt_amd_build_tree_size(ix, &nl, &ni, &nli)) return -1;
+  t.leaf_parent.resize(nl);
+  t.leaf_off.resize((size_t)nl + 1);
+  t.leaf_ids.resize(nli);
+  t.leaf_dists.resize(nli);
+  t.leaf_has_pivot.resize(nl);
+  t.leaf_pivot.resize((size_t)nl * row_bytes);
+  t.in_parent.resize(ni);
+  t.in_pivot.resize((size_t)ni * row_bytes);
+  t.in_child.resize((size_t)ni * 5);
+  t.in_border.resize((size_t)ni * 4);
+  return ngt_amd_build_get_tree(ix, t.leaf_parent.data(), t.leaf_off.data(), t.leaf_ids.data(), t.leaf_dists.data(),
+                                t.leaf_has_pivot.data(), t.leaf_pivot.data(), t.in_parent.data(), t.in_pivot.data(),
+                                t.in_child.data(), t.in_border.data());
+}
+
+int ngt_amd::build_tree_from_host(ngt_amd_index* ix, const HostTree& t, uint32_t n_internal, uint32_t root) {
+  return ngt_amd_build_set_tree(ix, t.leaf_parent.data(), t.leaf_off.data(), t.leaf_ids.data(), t.leaf_dists.data(),
+                                t.leaf_has_pivot.data(), t.leaf_pivot.data(), (uint32_t)t.leaf_parent.size(),
+                                t.in_parent.data(), t.in_pivot.data(), t.in_child.data(), t.in_border.data(),
+                                n_internal, root);
 }

@@ -26,7 +26,9 @@
 #include "accuracy_table.h"
 #include "coalesce.h"
 #include "edge_optimizer.h"
+#include "index_internal.h"
 #include "index_io.h"
+#include "knobs.h"
 
 using ngt_amd::HostIndex;
 using ngt_amd::HostProperty;
@@ -85,10 +87,7 @@ std::string rebuild_device(CapiIndex* ix) {
   HostIndex& h = ix->host;
   if (h.nrows < 2) return "the index is empty";
   if (!ix->dev) {
-    int dev = 0;
-    const char* env = getenv("NGT_AMD_DEVICE");
-    if (env) dev = atoi(env);
-    if (ngt_amd_index_create(&ix->dev, dev, h.prop.distance_type, h.prop.object_type,
+    if (ngt_amd_index_create(&ix->dev, ngt_amd::default_device(), h.prop.distance_type, h.prop.object_type,
                              (uint32_t)h.prop.object_dimension()))
       return amd_err();
   }
@@ -138,17 +137,8 @@ std::string run_search(CapiIndex* ix, const float* queries, uint32_t nq, size_t 
     n.assign(nq, 0);
     return "";
   }
-  ngt_amd_search_params p{};
-  p.k = (uint32_t)size;
-  p.epsilon = epsilon;
-  p.radius = radius < 0.0f ? FLT_MAX : radius;
-  p.edge_size = edge_size;
-  p.seed_mode = seed_mode;
-  p.all_leaf_nodes = 0;
-  // large indexes: visited epochs in HBM from the start (behind the LDS
-  // filter) instead of an LDS hash that would spill after a few thousand ids;
-  // identical results and distance counts either way
-  p.visited_hash_log2 = ix->host.nrows >= (1u << 18) ? -1 : 0;
+  const ngt_amd_search_params p = ngt_amd::library_search_params(
+      ix->host.nrows, (uint32_t)size, epsilon, radius < 0.0f ? FLT_MAX : radius, edge_size, seed_mode);
   ids.resize((size_t)nq * size);
   dists.resize((size_t)nq * size);
   n.resize(nq);
@@ -291,26 +281,12 @@ std::string fetch_session(CapiIndex* ix, bool after_build) {
   h.edge_off.assign(h.nrows + 1, ne);
   for (uint64_t v = 0; v <= h.nrows && v <= gsize; v++) h.edge_off[v] = off[v];
   if (after_build) h.prevsize.assign(h.nrows, 0);
-  uint32_t nl = 0, ni = 0;
-  uint64_t nli = 0;
-  if (ngt_amd_build_tree_size(ix->dev, &nl, &ni, &nli)) return amd_err();
+  ngt_amd::HostTree got;
+  if (ngt_amd::build_tree_to_host(ix->dev, h.row_bytes, got)) return amd_err();
   ngt_amd::HostTree& t = h.tree;
   const ngt_amd::HostTree before = after_build ? ngt_amd::HostTree() : t;
-  t = ngt_amd::HostTree();
-  t.leaf_parent.resize(nl);
-  t.leaf_off.resize((size_t)nl + 1);
-  t.leaf_ids.resize(nli);
-  t.leaf_dists.resize(nli);
-  t.leaf_has_pivot.resize(nl);
-  t.leaf_pivot.resize((size_t)nl * h.row_bytes);
-  t.in_parent.resize(ni);
-  t.in_pivot.resize((size_t)ni * h.row_bytes);
-  t.in_child.resize((size_t)ni * 5);
-  t.in_border.resize((size_t)ni * 4);
-  if (ngt_amd_build_get_tree(ix->dev, t.leaf_parent.data(), t.leaf_off.data(), t.leaf_ids.data(),
-                             t.leaf_dists.data(), t.leaf_has_pivot.data(), t.leaf_pivot.data(), t.in_parent.data(),
-                             t.in_pivot.data(), t.in_child.data(), t.in_border.data()))
-    return amd_err();
+  t = std::move(got);
+  const uint32_t nl = (uint32_t)t.leaf_parent.size(), ni = (uint32_t)t.in_parent.size();
   if (!after_build) {
     if (before.leaf_valid.size() != nl || before.in_valid.size() != (ni > 1 ? ni : before.in_valid.size()))
       return "the tree changed its node count during a removal";
@@ -364,14 +340,11 @@ std::string build_anng(CapiIndex* ix) {
   if (has_graph) {
     // incremental: the objects without a node join the existing graph and tree
     const ngt_amd::HostTree& t = h.tree;
-    const uint32_t nl = (uint32_t)t.leaf_parent.size(), ni = (uint32_t)t.in_parent.size();
+    const uint32_t ni = (uint32_t)t.in_parent.size();
     if (h.edge_off.size() < h.nrows + 1 || h.edge_dists.size() != h.edges.size())
       return "graph arrays inconsistent with the repository";
     if (ngt_amd_build_set_graph(ix->dev, h.edge_off.data(), h.edges.data(), h.edge_dists.data(), h.nrows) ||
-        ngt_amd_build_set_tree(ix->dev, t.leaf_parent.data(), t.leaf_off.data(), t.leaf_ids.data(),
-                               t.leaf_dists.data(), t.leaf_has_pivot.data(), t.leaf_pivot.data(), nl,
-                               t.in_parent.data(), t.in_pivot.data(), t.in_child.data(), t.in_border.data(),
-                               ni < 1 ? 1u : ni, t.root))
+        ngt_amd::build_tree_from_host(ix->dev, t, ni < 1 ? 1u : ni, t.root))
       return amd_err();
   }
   if (ngt_amd_build_insert(ix->dev, 1, h.nrows)) return amd_err();
@@ -427,15 +400,12 @@ std::string remove_objects(CapiIndex* ix, const uint32_t* ids, size_t n, std::ve
   p.seed_size = h.prop.seed_size;
   p.epsilon_for_creation = (float)h.prop.epsilon_for_creation;
   const ngt_amd::HostTree& t = h.tree;
-  const uint32_t nl = (uint32_t)t.leaf_parent.size(), ni = (uint32_t)t.in_parent.size();
+  const uint32_t ni = (uint32_t)t.in_parent.size();
   // from here on the device copy serves the session, whatever the outcome
   ix->device_stale = true;
   if (ngt_amd_build_begin(ix->dev, &p) ||
       ngt_amd_build_set_graph(ix->dev, h.edge_off.data(), h.edges.data(), h.edge_dists.data(), nodes) ||
-      ngt_amd_build_set_tree(ix->dev, t.leaf_parent.data(), t.leaf_off.data(), t.leaf_ids.data(),
-                             t.leaf_dists.data(), t.leaf_has_pivot.data(), t.leaf_pivot.data(), nl,
-                             t.in_parent.data(), t.in_pivot.data(), t.in_child.data(), t.in_border.data(),
-                             ni < 1 ? 1u : ni, t.root))
+      ngt_amd::build_tree_from_host(ix->dev, t, ni < 1 ? 1u : ni, t.root))
     return amd_err();
   if (ngt_amd_build_remove(ix->dev, ids, n, status.data())) return amd_err();
   bool any = false;
@@ -659,12 +629,8 @@ static std::string single_query(CapiIndex* ix, int kind, const float* q, size_t 
     std::shared_lock<std::shared_mutex> rd;
     std::string e = sync_device(ix, rd);
     if (!e.empty()) return e;
-    ngt_amd_search_params p{};
-    p.k = (uint32_t)size;
-    p.epsilon = epsilon;
-    p.radius = radius < 0.0f ? FLT_MAX : radius;
-    p.edge_size = edge_size;
-    p.seed_mode = seed_mode;
+    const ngt_amd_search_params p = ngt_amd::library_search_params(
+        ix->host.nrows, (uint32_t)size, epsilon, radius < 0.0f ? FLT_MAX : radius, edge_size, seed_mode);
     ids.resize(size);
     dists.resize(size);
     uint64_t c[NGT_AMD_COUNTERS_PER_QUERY];
@@ -1097,36 +1063,6 @@ bool null_optimizer(NGTError error, const char* func) {
   return param_error(error, func, "optimizer = 0");
 }
 
-std::string write_grp(const std::string& path, const HostIndex& h, const std::vector<uint64_t>& off,
-                      const std::vector<uint32_t>& ids, const std::vector<float>& dists) {
-  // GraphRepository::serialize (Graph.h:151-154), as index_io.cpp's save_index
-  FILE* f = fopen(path.c_str(), "wb");
-  if (!f) return "cannot write " + path;
-  std::vector<char> buf;
-  auto put = [&buf](const void* p, size_t n) { buf.insert(buf.end(), (const char*)p, (const char*)p + n); };
-  const uint64_t n = h.nrows;
-  put(&n, 8);
-  for (uint64_t i = 0; i < n; i++) {
-    // a slot holds a node when the input graph had one (an object, or edges)
-    if (i == 0 || (!h.valid[i] && h.edge_off[i] == h.edge_off[i + 1])) {
-      put("-", 1);
-      continue;
-    }
-    put("+", 1);
-    const uint32_t cnt = (uint32_t)(off[i + 1] - off[i]);
-    put(&cnt, 4);
-    for (uint64_t j = off[i]; j < off[i + 1]; j++) {
-      put(&ids[j], 4);
-      put(&dists[j], 4);
-    }
-  }
-  const uint32_t ps = (uint32_t)h.prevsize.size();
-  put(&ps, 4);
-  if (ps) put(h.prevsize.data(), (size_t)ps * 2);
-  const bool ok = fwrite(buf.data(), 1, buf.size(), f) == buf.size();
-  return (fclose(f) == 0 && ok) ? "" : "cannot write " + path;
-}
-
 // GraphOptimizer::execute (GraphOptimizer.h:230-300)
 std::string optimizer_execute(const CapiOptimizer& o, const std::string& in_path, const std::string& out_path) {
   if (o.search_parameter || o.prefetch_parameter || o.accuracy_table)
@@ -1153,17 +1089,16 @@ std::string optimizer_execute(const CapiOptimizer& o, const std::string& in_path
       p.path_adjustment = o.shortcut ? 1 : 0;
       p.input_is_anng = h.prop.graph_type == 1 ? 1 : 0;
       p.min_edges = o.min_edges;
-      int dev = 0;
-      if (const char* env = getenv("NGT_AMD_DEVICE")) dev = atoi(env);
       uint64_t ne = 0;
-      if (ngt_amd_onng_reconstruct(dev, h.edge_off.data(), h.edges.data(), h.edge_dists.data(), h.nrows, &p, &ne)) {
+      if (ngt_amd_onng_reconstruct(ngt_amd::default_device(), h.edge_off.data(), h.edges.data(), h.edge_dists.data(),
+                                   h.nrows, &p, &ne)) {
         e = amd_err();
       } else {
         std::vector<uint64_t> off(h.nrows + 1);
         std::vector<uint32_t> ids(ne);
         std::vector<float> dists(ne);
         if (ngt_amd_onng_get_graph(off.data(), ids.data(), dists.data())) e = amd_err();
-        if (e.empty()) e = write_grp(out_path + "/grp", h, off, ids, dists);
+        if (e.empty()) e = ngt_amd::write_grp(out_path + "/grp", h, off, ids, dists);
         if (e.empty() && edge) {
           h.prop.graph_type = 4;  // GraphTypeONNG
           e = ngt_amd::write_prf(out_path + "/prf", h.prop);

@@ -16,9 +16,11 @@
 #include <vector>
 
 #include "../../include/ngt_amd.h"
+#include "device_graph.h"
 #include "edge_optimizer.h"
 #include "edges_kernels.h"
 #include "index_internal.h"
+#include "index_io.h"
 #include "onng_kernels.h"
 
 using namespace ngt_amd;
@@ -26,34 +28,10 @@ using onng::Csr;
 
 namespace {
 
-struct DevGraph {
-  DevBuf<uint64_t> off;
-  DevBuf<uint32_t> ids;
-  DevBuf<float> d;
-  uint64_t edges = 0;
-  Csr csr() const { return Csr{off.p, ids.p, d.p}; }
-  void swap(DevGraph& o) {
-    std::swap(off.p, o.off.p);
-    std::swap(off.n, o.off.n);
-    std::swap(ids.p, o.ids.p);
-    std::swap(ids.n, o.ids.n);
-    std::swap(d.p, o.d.p);
-    std::swap(d.n, o.d.n);
-    std::swap(edges, o.edges);
-  }
-};
-
-template <typename T>
-int fetch(hipStream_t s, T* host, const T* dev, size_t count) {
-  HIP_OK(hipMemcpyAsync(host, dev, count * sizeof(T), hipMemcpyDeviceToHost, s));
-  HIP_OK(hipStreamSynchronize(s));
-  return 0;
-}
-
 // reconstructANNGFromANNG(G, K) -> out: count, scan, fill, then per list sort,
 // dedupe and unpack
-int recut_device(hipStream_t s, uint32_t n, Csr G, uint32_t K, DevGraph& out) {
-  DevBuf<uint32_t> cnt, cnt2;
+int recut_device(hipStream_t s, uint32_t n, Csr G, uint32_t K, DeviceGraph& out) {
+  DevBuf<uint32_t> cnt;
   DevBuf<uint64_t> loff, keys_a, keys_b;
   HIP_OK(cnt.alloc(n));
   HIP_OK(hipMemsetAsync(cnt.p, 0, (size_t)n * 4, s));
@@ -63,102 +41,34 @@ int recut_device(hipStream_t s, uint32_t n, Csr G, uint32_t K, DevGraph& out) {
   HIP_OK(hipGetLastError());
   uint64_t total = 0;
   if (fetch(s, &total, loff.p + n, 1)) return -1;
-  std::vector<uint32_t> h(n);
-  if (fetch(s, h.data(), cnt.p, n)) return -1;
   uint32_t longest = 0;
-  for (uint32_t x : h) longest = std::max(longest, x);
+  if (max_of(s, cnt.p, n, &longest)) return -1;
   HIP_OK(keys_a.alloc(total));
   HIP_OK(keys_b.alloc(total));
   HIP_OK(hipMemsetAsync(cnt.p, 0, (size_t)n * 4, s));
   edges::fill_recut(n, G, K, loff.p, cnt.p, keys_a.p, s);
-  onng::sort_lists(n, loff.p, keys_a.p, keys_b.p, longest > onng::kFastCap, s);
-  HIP_OK(cnt2.alloc(n));
-  HIP_OK(hipMemsetAsync(cnt2.p, 0, (size_t)n * 4, s));
-  onng::unique_lists(n, loff.p, keys_b.p, keys_a.p, cnt2.p, s);
-  HIP_OK(out.off.alloc((size_t)n + 1));
-  onng::scan_u32(cnt2.p, n, out.off.p, s);
-  HIP_OK(hipGetLastError());
-  if (fetch(s, &out.edges, out.off.p + n, 1)) return -1;
-  HIP_OK(out.ids.alloc(out.edges));
-  HIP_OK(out.d.alloc(out.edges));
-  onng::unpack_lists(n, loff.p, keys_a.p, out.off.p, out.ids.p, out.d.p, s);
-  HIP_OK(hipGetLastError());
-  HIP_OK(hipStreamSynchronize(s));
-  return 0;
+  return lists_from_keys(s, n, loff.p, keys_a, keys_b, longest, out);
 }
 
-struct Stream {
-  hipStream_t s = nullptr;
-  ~Stream() {
-    if (s) (void)hipStreamDestroy(s);
-  }
-};
-
-struct Result {
-  std::vector<uint64_t> off;
-  std::vector<uint32_t> ids;
-  std::vector<float> d;
-  bool ready = false;
-};
-thread_local Result t_result;
+thread_local HostGraph t_graph;
 thread_local std::vector<ngt_amd_edge_sample> t_trace;  // the samples of the thread's last optimisation
 
-int download(hipStream_t s, uint32_t n, const DevGraph& g, std::vector<uint64_t>& off, std::vector<uint32_t>& ids,
-             std::vector<float>& d) {
-  off.resize((size_t)n + 1);
-  ids.resize(g.edges);
-  d.resize(g.edges);
-  HIP_OK(hipMemcpyAsync(off.data(), g.off.p, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, s));
-  if (g.edges) HIP_OK(hipMemcpyAsync(ids.data(), g.ids.p, g.edges * 4, hipMemcpyDeviceToHost, s));
-  if (g.edges) HIP_OK(hipMemcpyAsync(d.data(), g.d.p, g.edges * 4, hipMemcpyDeviceToHost, s));
-  HIP_OK(hipStreamSynchronize(s));
-  return 0;
-}
-
-int upload(hipStream_t s, uint32_t n, const uint64_t* off, const uint32_t* ids, const float* d, DevGraph& g) {
-  const uint64_t E = off[n];
-  HIP_OK(g.off.alloc((size_t)n + 1));
-  HIP_OK(g.ids.alloc(E));
-  HIP_OK(g.d.alloc(E));
-  HIP_OK(hipMemcpyAsync(g.off.p, off, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, s));
-  if (E) HIP_OK(hipMemcpyAsync(g.ids.p, ids, E * 4, hipMemcpyHostToDevice, s));
-  if (E) HIP_OK(hipMemcpyAsync(g.d.p, d, E * 4, hipMemcpyHostToDevice, s));
-  g.edges = E;
-  return 0;
-}
-
 int recut_host_graph(int device, const uint64_t* offsets, const uint32_t* ids, const float* dists, uint64_t nrows,
-                     uint32_t K, Result& res) {
+                     uint32_t K, HostGraph& res) {
   res.ready = false;
-  if (nrows == 0 || nrows >= (1ull << 31)) return fail("ngt_amd_recut_anng: %llu rows are not supported", (unsigned long long)nrows);
+  uint32_t longest = 0;
+  if (check_csr("ngt_amd_recut_anng", offsets, ids, dists, nrows, false, &longest)) return -1;
   if (K == 0) return fail("ngt_amd_recut_anng: K must be positive");
-  if (offsets[0] != 0) return fail("ngt_amd_recut_anng: offsets[0] is not 0");
-  for (uint64_t v = 0; v < nrows; v++) {
-    if (offsets[v + 1] < offsets[v]) return fail("ngt_amd_recut_anng: offsets decrease at node %llu", (unsigned long long)v);
-    if (offsets[v + 1] - offsets[v] >= (1ull << 31)) return fail("ngt_amd_recut_anng: the list of node %llu is too long", (unsigned long long)v);
-  }
-  if (offsets[nrows] && (!ids || !dists)) return fail("ngt_amd_recut_anng: ids or dists is null");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-    return fail("ngt_amd_recut_anng: no HIP device available (the MI355X path has no CPU fallback)");
-  if (device < 0 || device >= ndev) return fail("ngt_amd_recut_anng: device %d out of range", device);
-  HIP_OK(hipSetDevice(device));
-  Stream st;
-  HIP_OK(hipStreamCreateWithFlags(&st.s, hipStreamDefault));
+  if (select_device("ngt_amd_recut_anng", device)) return -1;
+  OwnedStream st;
+  if (st.create()) return -1;
   const uint32_t n = (uint32_t)nrows;
-  DevGraph in, out;
-  if (upload(st.s, n, offsets, ids, dists, in)) return -1;
-  DevBuf<uint32_t> d_err;
-  HIP_OK(d_err.alloc(onng::kErrWords));
-  HIP_OK(hipMemsetAsync(d_err.p, 0xff, onng::kErrWords * 4, st.s));
-  onng::check_lists(n, in.csr(), d_err.p, st.s);
-  HIP_OK(hipGetLastError());
-  uint32_t err[onng::kErrWords];
-  if (fetch(st.s, err, d_err.p, onng::kErrWords)) return -1;
-  if (err[onng::kErrBadId] != 0xffffffffu)
-    return fail("ngt_amd_recut_anng: the list of node %u holds an id outside [1, %u)", err[onng::kErrBadId], n);
+  DeviceGraph in, out;
+  if (upload_graph(st.s, n, offsets, ids, dists, in)) return -1;
+  DevBuf<uint32_t> err;
+  if (verify_lists("ngt_amd_recut_anng", st.s, n, in, false, err)) return -1;
   if (recut_device(st.s, n, in.csr(), K, out)) return -1;
-  if (download(st.s, n, out, res.off, res.ids, res.d)) return -1;
+  if (download_graph(st.s, n, out, res)) return -1;
   res.ready = true;
   return 0;
 }
@@ -167,62 +77,27 @@ double ms_since(std::chrono::steady_clock::time_point t0) {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
-// The session's tree as the getters return it.
-struct TreeCopy {
-  std::vector<uint32_t> leaf_parent, leaf_ids, in_parent, in_child;
-  std::vector<uint64_t> leaf_off;
-  std::vector<float> leaf_dists, in_border;
-  std::vector<uint8_t> leaf_has_pivot, leaf_pivot, in_pivot;
-  uint32_t nl = 0, ni = 0, root = 0;
-};
-
 struct Optimizer {
   ngt_amd_index* ix;
   ngt_amd_build_params bp;
-  Stream st;
+  OwnedStream st;
   GlibcRandHost rnd;
   // the last sample's state on the host: the graph the next construction starts
   // from (after a sample: its last re-cut), the nodes it holds, its tree
-  std::vector<uint64_t> h_off;
-  std::vector<uint32_t> h_ids;
-  std::vector<float> h_d;
+  HostGraph h;
   std::vector<uint8_t> node;
   uint64_t graph_rows = 0;
   bool have_prev = false, cut_since_build = false;
-  TreeCopy tree;
-  DevGraph src, cur;  // the sample's graph; the re-cut the index searches
+  HostTree tree;
+  DeviceGraph src, cur;  // the sample's graph; the re-cut the index searches
   std::vector<double> build_ms, recut_ms, search_ms;
 
   ~Optimizer() {
     // an index that still reads the last re-cut takes its buffers over
     if (cur.off.p && ix->edge_off.p == cur.off.p && ix->edges.p == cur.ids.p) {
-      ix->edge_off.owned = true;
-      ix->edges.owned = true;
-      cur.off.owned = false;
-      cur.ids.owned = false;
+      ix->edge_off.take_from(cur.off);
+      ix->edges.take_from(cur.ids);
     }
-  }
-
-  int fetch_tree() {
-    uint64_t nli = 0;
-    if (ngt_amd_build_tree_size(ix, &tree.nl, &tree.ni, &nli)) return -1;
-    const uint64_t rb = ix->row_bytes;
-    tree.leaf_parent.resize(tree.nl);
-    tree.leaf_off.resize((size_t)tree.nl + 1);
-    tree.leaf_ids.resize(nli);
-    tree.leaf_dists.resize(nli);
-    tree.leaf_has_pivot.resize(tree.nl);
-    tree.leaf_pivot.resize((size_t)tree.nl * rb);
-    tree.in_parent.resize(tree.ni);
-    tree.in_pivot.resize((size_t)tree.ni * rb);
-    tree.in_child.resize((size_t)tree.ni * 5);
-    tree.in_border.resize((size_t)tree.ni * 4);
-    if (ngt_amd_build_get_tree(ix, tree.leaf_parent.data(), tree.leaf_off.data(), tree.leaf_ids.data(),
-                               tree.leaf_dists.data(), tree.leaf_has_pivot.data(), tree.leaf_pivot.data(),
-                               tree.in_parent.data(), tree.in_pivot.data(), tree.in_child.data(), tree.in_border.data()))
-      return -1;
-    tree.root = ix->build->root;
-    return 0;
   }
 
   // createIndex(threads, end_id) into the graph and tree the sample before left
@@ -230,13 +105,13 @@ struct Optimizer {
     const auto t0 = std::chrono::steady_clock::now();
     const uint32_t n = (uint32_t)ix->nrows;
     if (cut_since_build) {  // the previous sample's last re-cut is the graph now
-      if (download(st.s, n, cur, h_off, h_ids, h_d)) return -1;
+      if (download_graph(st.s, n, cur, h)) return -1;
       cut_since_build = false;
     }
     if (ngt_amd_build_begin(ix, &bp)) return -1;
     ix->build->rnd = rnd;  // the stream goes on where the query draw left it
     if (have_prev) {
-      if (ngt_amd_build_set_graph(ix, h_off.data(), h_ids.data(), h_d.data(), graph_rows)) return -1;
+      if (ngt_amd_build_set_graph(ix, h.off.data(), h.ids.data(), h.d.data(), graph_rows)) return -1;
       // a node whose re-cut list came out empty is still a node: not inserted again
       BuildState& b = *ix->build;
       for (uint64_t v = 0; v < graph_rows; v++)
@@ -244,30 +119,28 @@ struct Optimizer {
           b.in_graph[v] = 1;
           b.graph_size = std::max<uint64_t>(b.graph_size, v + 1);
         }
-      if (ngt_amd_build_set_tree(ix, tree.leaf_parent.data(), tree.leaf_off.data(), tree.leaf_ids.data(),
-                                 tree.leaf_dists.data(), tree.leaf_has_pivot.data(), tree.leaf_pivot.data(), tree.nl,
-                                 tree.in_parent.data(), tree.in_pivot.data(), tree.in_child.data(),
-                                 tree.in_border.data(), tree.ni, tree.root))
-        return -1;
+      if (build_tree_from_host(ix, tree, (uint32_t)tree.in_parent.size(), tree.root)) return -1;
     }
     if (ngt_amd_build_insert(ix, 1, end_id)) return -1;
     rnd = ix->build->rnd;
     uint64_t gsize = 0, ne = 0;
     if (ngt_amd_build_graph_size(ix, &gsize, &ne)) return -1;
     std::vector<uint64_t> off(gsize + 1);
-    h_ids.resize(ne);
-    h_d.resize(ne);
-    if (ngt_amd_build_get_graph(ix, off.data(), h_ids.data(), h_d.data())) return -1;
-    h_off.assign((size_t)n + 1, ne);
-    for (uint64_t v = 0; v <= gsize && v <= n; v++) h_off[v] = off[v];
+    h.ids.resize(ne);
+    h.d.resize(ne);
+    if (ngt_amd_build_get_graph(ix, off.data(), h.ids.data(), h.d.data())) return -1;
+    h.off.assign((size_t)n + 1, ne);
+    for (uint64_t v = 0; v <= gsize && v <= n; v++) h.off[v] = off[v];
     graph_rows = gsize;
     node.assign(ix->build->in_graph.begin(), ix->build->in_graph.end());
-    if (fetch_tree()) return -1;
+    if (build_tree_to_host(ix, ix->row_bytes, tree)) return -1;
+    tree.root = ix->build->root;
     have_prev = true;
     // the pseudo ground truth searches the sample's whole graph
-    if (ngt_amd_index_set_graph(ix, h_off.data(), h_ids.data(), ne)) return -1;
-    if (ngt_amd_index_set_tree(ix, tree.in_pivot.data(), tree.ni, tree.in_child.data(), tree.in_border.data(), 5,
-                               tree.root, tree.leaf_off.data(), tree.nl, tree.leaf_ids.data(), tree.leaf_ids.size()))
+    if (ngt_amd_index_set_graph(ix, h.off.data(), h.ids.data(), ne)) return -1;
+    if (ngt_amd_index_set_tree(ix, tree.in_pivot.data(), (uint32_t)tree.in_parent.size(), tree.in_child.data(),
+                               tree.in_border.data(), 5, tree.root, tree.leaf_off.data(),
+                               (uint32_t)tree.leaf_parent.size(), tree.leaf_ids.data(), tree.leaf_ids.size()))
       return -1;
     build_ms.push_back(ms_since(t0));
     recut_ms.push_back(0.0);
@@ -277,7 +150,7 @@ struct Optimizer {
 
   int extract() {
     const auto t0 = std::chrono::steady_clock::now();
-    if (upload(st.s, (uint32_t)ix->nrows, h_off.data(), h_ids.data(), h_d.data(), src)) return -1;
+    if (upload_graph(st.s, (uint32_t)ix->nrows, h.off.data(), h.ids.data(), h.d.data(), src)) return -1;
     HIP_OK(hipStreamSynchronize(st.s));
     recut_ms.back() += ms_since(t0);
     return 0;
@@ -285,7 +158,7 @@ struct Optimizer {
 
   int recut(size_t K) {
     const auto t0 = std::chrono::steady_clock::now();
-    DevGraph next;
+    DeviceGraph next;
     if (recut_device(st.s, (uint32_t)ix->nrows, src.csr(), (uint32_t)std::min<size_t>(K, 0xffffffffu), next)) return -1;
     if (ngt_amd_index_set_graph_device(ix, next.off.p, next.ids.p, next.edges)) return -1;
     cur.swap(next);  // the index reads `cur` from here on; the one before is freed
@@ -325,7 +198,7 @@ int optimize_edges(ngt_amd_index* ix, const ngt_amd_edge_params* prm, uint64_t* 
   o.ix = ix;
   o.bp = prm->build;
   o.bp.edge_size_for_creation = (int32_t)std::max<uint64_t>(P.max_edges, 1);
-  HIP_OK(hipStreamCreateWithFlags(&o.st.s, hipStreamDefault));
+  if (o.st.create()) return -1;
   o.rnd.seed(1);  // a fresh process's rand() stream
 
   // ---- extractAndRemoveRandomQueries
@@ -361,13 +234,8 @@ int optimize_edges(ngt_amd_index* ix, const ngt_amd_edge_params* prm, uint64_t* 
   cb.recut = [&](size_t K) -> std::string { return o.recut(K) ? ngt_amd_last_error() : ""; };
   cb.search = [&](AccuracyBatch& b) -> std::string {
     const auto t0 = std::chrono::steady_clock::now();
-    ngt_amd_search_params p{};
-    p.k = (uint32_t)b.size;
-    p.epsilon = b.epsilon;
-    p.radius = -1.0f;  // FLT_MAX
-    p.edge_size = b.edge_size;
-    p.seed_mode = NGT_AMD_SEED_TREE;
-    p.visited_hash_log2 = ix->nrows >= (1u << 18) ? -1 : 0;
+    const ngt_amd_search_params p = library_search_params(ix->nrows, (uint32_t)b.size, b.epsilon, -1.0f /* FLT_MAX */,
+                                                          b.edge_size, NGT_AMD_SEED_TREE);
     cnt.assign((size_t)b.nq * NGT_AMD_COUNTERS_PER_QUERY, 0);
     if (ngt_amd_search(ix, &p, b.queries, b.nq, nullptr, nullptr, b.ids.data(), b.dists.data(), b.n.data(),
                        cnt.data()))
@@ -425,21 +293,16 @@ extern "C" int ngt_amd_recut_anng(int device, const uint64_t* offsets, const uin
                                   uint64_t nrows, uint32_t K, uint64_t* out_nedges) {
   if (!offsets || !out_nedges) return fail("ngt_amd_recut_anng: bad arguments");
   *out_nedges = 0;
-  if (recut_host_graph(device, offsets, ids, dists, nrows, K, t_result)) {
-    t_result = Result();
+  if (recut_host_graph(device, offsets, ids, dists, nrows, K, t_graph)) {
+    t_graph = HostGraph();
     return -1;
   }
-  *out_nedges = t_result.ids.size();
+  *out_nedges = t_graph.ids.size();
   return 0;
 }
 
 extern "C" int ngt_amd_recut_get_graph(uint64_t* offsets, uint32_t* ids, float* dists) {
-  if (!t_result.ready) return fail("ngt_amd_recut_get_graph: no re-cut graph on this thread");
-  if (!offsets) return fail("ngt_amd_recut_get_graph: bad arguments");
-  memcpy(offsets, t_result.off.data(), t_result.off.size() * 8);
-  if (ids && !t_result.ids.empty()) memcpy(ids, t_result.ids.data(), t_result.ids.size() * 4);
-  if (dists && !t_result.d.empty()) memcpy(dists, t_result.d.data(), t_result.d.size() * 4);
-  return 0;
+  return copy_out(t_graph, "ngt_amd_recut_get_graph", "re-cut", offsets, ids, dists);
 }
 
 extern "C" int ngt_amd_optimize_edges(ngt_amd_index* ix, const ngt_amd_edge_params* prm, uint64_t* edge,

@@ -26,14 +26,26 @@ int fail(const char* fmt, ...);
       return ngt_amd::fail("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
   } while (0)
 
+// Bytes held by the buffers that point at it, and the most they ever held.
+struct DevMeter {
+  size_t cur = 0, peak = 0;
+};
+
 template <typename T>
 struct DevBuf {
   T* p = nullptr;
   size_t n = 0;
   bool owned = true;
+  DevMeter* meter = nullptr;  // optional: charged in alloc, credited in release
+  DevBuf() {}
+  explicit DevBuf(DevMeter* m) : meter(m) {}
   ~DevBuf() { release(); }
+  size_t bytes() const { return std::max<size_t>(n, 1) * sizeof(T); }
   void release() {
-    if (p && owned) (void)hipFree(p);
+    if (p && owned) {
+      (void)hipFree(p);
+      if (meter) meter->cur -= bytes();
+    }
     p = nullptr;
     n = 0;
     owned = true;
@@ -41,8 +53,37 @@ struct DevBuf {
   hipError_t alloc(size_t count) {
     if (p && owned && n >= count) return hipSuccess;
     release();
+    hipError_t e = hipMalloc((void**)&p, std::max<size_t>(count, 1) * sizeof(T));
+    if (e != hipSuccess) {
+      p = nullptr;
+      return e;
+    }
     n = count;
-    return hipMalloc((void**)&p, std::max<size_t>(count, 1) * sizeof(T));
+    if (meter) {
+      meter->cur += bytes();
+      meter->peak = std::max(meter->peak, meter->cur);
+    }
+    return hipSuccess;
+  }
+  void swap(DevBuf& o) {
+    std::swap(p, o.p);
+    std::swap(n, o.n);
+    std::swap(owned, o.owned);
+    std::swap(meter, o.meter);
+  }
+  // point at memory owned elsewhere
+  void borrow(T* ptr, size_t count) {
+    release();
+    p = ptr;
+    n = count;
+    owned = false;
+  }
+  // own what this buffer borrowed from o; o lets go of it
+  void take_from(DevBuf& o) {
+    owned = true;
+    if (o.p && o.owned && o.meter) o.meter->cur -= o.bytes();
+    o.owned = false;
+    o.release();
   }
   hipError_t upload_async(const T* h, size_t count, hipStream_t s) {
     hipError_t e = alloc(count);
@@ -357,5 +398,14 @@ std::vector<uint32_t> random_seed_lists(ngt_amd_index* ix, uint32_t nq, std::vec
 // host float queries [nq][dim] -> prepared device rows (Index::allocateObject)
 int upload_queries(ngt_amd_index* ix, const void* queries, uint32_t nq, DevBuf<float>& raw,
                    DevBuf<uint8_t>& prep, hipStream_t s);
+// the parameters of the library's own searches of an index of nrows slots
+ngt_amd_search_params library_search_params(uint64_t nrows, uint32_t k, float epsilon, float radius,
+                                            int64_t edge_size, int seed_mode);
+// A build session's tree (build.cpp) to and from the host arrays of index_io.h:
+// the node arrays sized and filled by ngt_amd_build_get_tree, and handed to
+// ngt_amd_build_set_tree.  leaf_valid, in_valid, root and present are the caller's.
+struct HostTree;
+int build_tree_to_host(const ngt_amd_index* ix, uint64_t row_bytes, HostTree& t);
+int build_tree_from_host(ngt_amd_index* ix, const HostTree& t, uint32_t n_internal, uint32_t root);
 
 }  // namespace ngt_amd

@@ -318,6 +318,31 @@ std::string load_index(const std::string& dir, HostIndex& ix) {
   return "";
 }
 
+// GraphRepository::serialize (Graph.h:151-154)
+std::string write_grp(const std::string& path, const HostIndex& h, const std::vector<uint64_t>& off,
+                      const std::vector<uint32_t>& ids, const std::vector<float>& dists) {
+  Writer w(path);
+  if (!w.f) return "cannot write " + path;
+  w.put<uint64_t>(h.nrows);
+  for (uint64_t i = 0; i < h.nrows; i++) {
+    // a slot holds a node when h's graph has one (an object, or edges)
+    if (i == 0 || (!h.valid[i] && h.edge_off[i] == h.edge_off[i + 1])) {
+      w.put<char>('-');
+      continue;
+    }
+    w.put<char>('+');
+    w.put<uint32_t>((uint32_t)(off[i + 1] - off[i]));
+    for (uint64_t j = off[i]; j < off[i + 1]; j++) {
+      w.put<uint32_t>(ids[j]);
+      w.put<float>(j < dists.size() ? dists[j] : 0.f);
+    }
+  }
+  w.put<uint32_t>((uint32_t)h.prevsize.size());
+  for (uint16_t v : h.prevsize) w.put<uint16_t>(v);
+  w.f.close();
+  return w.f ? "" : "cannot write " + path;
+}
+
 std::string save_index(const std::string& dir, HostIndex& ix) {
   std::string e = write_prf(dir + "/prf", ix.prop);
   if (!e.empty()) return e;
@@ -335,26 +360,7 @@ std::string save_index(const std::string& dir, HostIndex& ix) {
       }
     }
   }
-  {
-    Writer w(dir + "/grp");
-    if (!w.f) return "cannot write grp";
-    w.put<uint64_t>(ix.nrows);
-    for (uint64_t i = 0; i < ix.nrows; i++) {
-      uint64_t b = ix.edge_off[i], en = ix.edge_off[i + 1];
-      if (i == 0 || (!ix.valid[i] && b == en)) {
-        w.put<char>('-');
-        continue;
-      }
-      w.put<char>('+');
-      w.put<uint32_t>((uint32_t)(en - b));
-      for (uint64_t j = b; j < en; j++) {
-        w.put<uint32_t>(ix.edges[j]);
-        w.put<float>(j < ix.edge_dists.size() ? ix.edge_dists[j] : 0.f);
-      }
-    }
-    w.put<uint32_t>((uint32_t)ix.prevsize.size());
-    for (uint16_t v : ix.prevsize) w.put<uint16_t>(v);
-  }
+  if (!write_grp(dir + "/grp", ix, ix.edge_off, ix.edges, ix.edge_dists).empty()) return "cannot write grp";
   if (ix.tree.present) {
     HostTree& t = ix.tree;
     Writer w(dir + "/tre");

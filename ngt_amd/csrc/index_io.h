@@ -96,6 +96,10 @@ std::string read_prf(const std::string& path, HostProperty& p);
 std::string write_prf(const std::string& path, HostProperty& p);
 std::string load_index(const std::string& dir, HostIndex& ix);
 std::string save_index(const std::string& dir, HostIndex& ix);
+// the grp file of h's node repository with the lists of off/ids/dists (a
+// distance past the end of dists is written as 0); prevsize comes from h
+std::string write_grp(const std::string& path, const HostIndex& h, const std::vector<uint64_t>& off,
+                      const std::vector<uint32_t>& ids, const std::vector<float>& dists);
 std::string load_qg(const std::string& dir, uint64_t nrows, HostQuantizer& q);
 
 }  // namespace ngt_amd

@@ -22,4 +22,10 @@ inline bool test_knobs_enabled() {
 
 inline const char* knob(const char* name) { return test_knobs_enabled() ? std::getenv(name) : nullptr; }
 
+// the device a C-API index opens on
+inline int default_device() {
+  const char* v = std::getenv("NGT_AMD_DEVICE");
+  return v ? std::atoi(v) : 0;
+}
+
 }  // namespace ngt_amd

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "../../include/ngt_amd.h"
+#include "device_graph.h"
 #include "index_internal.h"
 #include "ngt_kernels.h"
 #include "prep_kernels.h"
@@ -56,11 +57,7 @@ extern "C" int ngt_amd_index_create(ngt_amd_index** out, int device, int distanc
   if (!valid_metric(distance_type)) return fail("ngt_amd_index_create: invalid distance type %d", distance_type);
   if (object_type != 1 && object_type != 2) return fail("ngt_amd_index_create: invalid object type %d", object_type);
   if (dimension == 0) return fail("ngt_amd_index_create: dimension is 0");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-    return fail("ngt_amd_index_create: no HIP device available (the MI355X path has no CPU fallback)");
-  if (device < 0 || device >= ndev) return fail("ngt_amd_index_create: device %d out of range", device);
-  HIP_OK(hipSetDevice(device));
+  if (select_device("ngt_amd_index_create", device)) return -1;
   hipDeviceProp_t prop;
   HIP_OK(hipGetDeviceProperties(&prop, device));
   auto* ix = new ngt_amd_index();
@@ -209,12 +206,8 @@ extern "C" int ngt_amd_index_set_graph_device(ngt_amd_index* ix, const uint64_t*
   if (!ix || !d_offsets) return fail("ngt_amd_index_set_graph_device: bad arguments");
   HIP_OK(hipSetDevice(ix->device));
   ServeHold serve_hold(ix);
-  ix->edge_off.release();
-  ix->edges.release();
-  ix->edge_off.p = const_cast<uint64_t*>(d_offsets);
-  ix->edge_off.owned = false;
-  ix->edges.p = const_cast<uint32_t*>(d_edges);
-  ix->edges.owned = false;
+  ix->edge_off.borrow(const_cast<uint64_t*>(d_offsets), ix->nrows + 1);
+  ix->edges.borrow(const_cast<uint32_t*>(d_edges), nedges);
   ix->nedges = nedges;
   ix->has_graph = true;
   std::vector<uint64_t> h(ix->nrows + 1);
@@ -858,6 +851,21 @@ extern "C" int ngt_amd_prepare_queries_device(ngt_amd_index* ix, const float* d_
   bool normalize = ix->metric == 5 || ix->metric == 6 || ix->metric == 9;
   HIP_OK(launch_prepare_queries(d_in, ix->dim, nq, ix->dp, ix->otype, normalize, d_out, c->err.p, s));
   return 0;
+}
+
+ngt_amd_search_params ngt_amd::library_search_params(uint64_t nrows, uint32_t k, float epsilon, float radius,
+                                                     int64_t edge_size, int seed_mode) {
+  ngt_amd_search_params p{};
+  p.k = k;
+  p.epsilon = epsilon;
+  p.radius = radius;
+  p.edge_size = edge_size;
+  p.seed_mode = seed_mode;
+  // large indexes: visited epochs in HBM from the start (behind the LDS
+  // filter) instead of an LDS hash that would spill after a few thousand ids;
+  // identical results and distance counts either way
+  p.visited_hash_log2 = nrows >= (1u << 18) ? -1 : 0;
+  return p;
 }
 
 extern "C" int ngt_amd_search(ngt_amd_index* ix, const ngt_amd_search_params* prm, const void* queries,

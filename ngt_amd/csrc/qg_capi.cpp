@@ -25,6 +25,7 @@
 #include "index_internal.h"
 #include "index_io.h"
 #include "kmeans_ngt.h"
+#include "knobs.h"
 
 namespace {
 
@@ -52,9 +53,7 @@ std::string open_device(QgCapiIndex* ix, uint32_t max_edges) {
   HostIndex& h = ix->host;
   if (h.prop.distance_type != NGT_AMD_DISTANCE_L2 || h.prop.object_type != NGT_AMD_OBJECT_FLOAT)
     return "NGTQG supports L2 float indexes only";
-  int dev = 0;
-  if (const char* env = getenv("NGT_AMD_DEVICE")) dev = atoi(env);
-  if (ngt_amd_index_create(&ix->dev, dev, h.prop.distance_type, h.prop.object_type, (uint32_t)h.prop.dimension))
+  if (ngt_amd_index_create(&ix->dev, ngt_amd::default_device(), h.prop.distance_type, h.prop.object_type, (uint32_t)h.prop.dimension))
     return amd_err();
   if (ngt_amd_index_set_objects(ix->dev, h.rows.data(), h.nrows, h.valid.data())) return amd_err();
   if (ngt_amd_index_set_graph(ix->dev, h.edge_off.data(), h.edges.data(), h.edges.size())) return amd_err();
@@ -367,9 +366,7 @@ bool ngtqg_quantize(const char* indexPath, NGTQGQuantizationParameters parameter
   for (uint64_t i = 1; i < h.nrows; i++) nvalid += h.valid[i] ? 1 : 0;
   if (nvalid < 16) return err("at least 16 objects are needed to train 16 centroids per subspace");
   QgCapiIndex ix;
-  int dev = 0;
-  if (const char* env = getenv("NGT_AMD_DEVICE")) dev = atoi(env);
-  if (ngt_amd_index_create(&ix.dev, dev, h.prop.distance_type, h.prop.object_type, dim)) return err(amd_err());
+  if (ngt_amd_index_create(&ix.dev, ngt_amd::default_device(), h.prop.distance_type, h.prop.object_type, dim)) return err(amd_err());
   if (ngt_amd_index_set_objects(ix.dev, h.rows.data(), h.nrows, h.valid.data())) return err(amd_err());
   std::vector<float> local;
   e = train_local_kmeans_ngt(h, M, (uint32_t)dsub, local);

@@ -17,14 +17,13 @@
 #include <float.h>
 #include <limits.h>
 #include <stdint.h>
-#include <string.h>
 
 #include <algorithm>
 #include <chrono>
 #include <mutex>
-#include <vector>
 
 #include "../../include/ngt_amd.h"
+#include "device_graph.h"
 #include "index_internal.h"
 #include "prep_kernels.h"
 #include "refine_kernels.h"
@@ -35,25 +34,6 @@ using namespace ngt_amd::refine;
 namespace {
 
 constexpr uint32_t kNone = 0xffffffffu;
-
-struct Graph {
-  DevBuf<uint64_t> off;
-  DevBuf<uint32_t> ids;
-  DevBuf<float> d;
-  uint64_t edges = 0;
-  uint32_t maxlen = 0;
-  Csr csr() const { return Csr{off.p, ids.p, d.p}; }
-  void swap(Graph& o) {
-    std::swap(off.p, o.off.p);
-    std::swap(off.n, o.off.n);
-    std::swap(ids.p, o.ids.p);
-    std::swap(ids.n, o.ids.n);
-    std::swap(d.p, o.d.p);
-    std::swap(d.n, o.d.n);
-    std::swap(edges, o.edges);
-    std::swap(maxlen, o.maxlen);
-  }
-};
 
 // Buffers kept from batch to batch.  words: the two error words, then the
 // longest batch list, the most candidates of a target, the longest new list.
@@ -67,55 +47,18 @@ struct Work {
   ngt_amd_refine_stats st{};
 };
 
-template <typename T>
-int fetch(Work& W, T* host, const T* dev, size_t count) {
-  HIP_OK(hipMemcpyAsync(host, dev, count * sizeof(T), hipMemcpyDeviceToHost, W.s));
-  HIP_OK(hipStreamSynchronize(W.s));
-  return 0;
-}
-
-int upload_graph(Work& W, const uint64_t* offsets, const uint32_t* ids, const float* dists, Graph& G) {
-  const uint32_t n = W.n;
-  const uint64_t E = offsets[n];
-  HIP_OK(G.off.alloc((size_t)n + 1));
-  HIP_OK(G.ids.alloc(E));
-  HIP_OK(G.d.alloc(E));
-  HIP_OK(hipMemcpyAsync(G.off.p, offsets, ((size_t)n + 1) * 8, hipMemcpyHostToDevice, W.s));
-  if (E) HIP_OK(hipMemcpyAsync(G.ids.p, ids, E * 4, hipMemcpyHostToDevice, W.s));
-  if (E) HIP_OK(hipMemcpyAsync(G.d.p, dists, E * 4, hipMemcpyHostToDevice, W.s));
-  G.edges = E;
-  // every list in (distance, id) order with ids of rows: lower_bound needs it
+// The graph into HBM, refused unless every list is in (distance, id) order with
+// ids of rows: lower_bound needs it.
+int upload_lists(Work& W, const uint64_t* offsets, const uint32_t* ids, const float* dists, uint32_t longest,
+                 DeviceGraph& G) {
+  if (upload_graph(W.s, W.n, offsets, ids, dists, G)) return -1;
+  G.maxlen = longest;
   DevBuf<uint32_t> err;
-  HIP_OK(err.alloc(onng::kErrWords));
-  HIP_OK(hipMemsetAsync(err.p, 0xff, onng::kErrWords * 4, W.s));
-  onng::check_lists(n, G.csr(), err.p, W.s);
-  HIP_OK(hipGetLastError());
-  uint32_t h[onng::kErrWords];
-  if (fetch(W, h, err.p, onng::kErrWords)) return -1;
-  if (h[onng::kErrBadId] != kNone) return fail("refine: the list of node %u holds an id outside [1, %u)", h[onng::kErrBadId], n);
-  if (h[onng::kErrOrder] != kNone) return fail("refine: the list of node %u is not in (distance, id) order", h[onng::kErrOrder]);
-  return 0;
-}
-
-// host-side checks of a CSR graph; the longest list goes to *longest
-int check_csr(const char* who, const uint64_t* offsets, const uint32_t* ids, const float* dists, uint64_t nrows,
-              uint32_t* longest) {
-  if (!offsets) return fail("%s: bad arguments", who);
-  if (nrows == 0 || nrows >= (1ull << 31)) return fail("%s: %llu rows are not supported", who, (unsigned long long)nrows);
-  if (offsets[0] != 0) return fail("%s: offsets[0] is not 0", who);
-  *longest = 0;
-  for (uint64_t v = 0; v < nrows; v++) {
-    if (offsets[v + 1] < offsets[v]) return fail("%s: offsets decrease at node %llu", who, (unsigned long long)v);
-    if (offsets[v + 1] - offsets[v] >= (1ull << 31)) return fail("%s: the list of node %llu is too long", who, (unsigned long long)v);
-    *longest = std::max(*longest, (uint32_t)(offsets[v + 1] - offsets[v]));
-  }
-  if (offsets[1] != 0) return fail("%s: slot 0 is the dummy and has no list", who);
-  if (offsets[nrows] && (!ids || !dists)) return fail("%s: ids or dists is null", who);
-  return 0;
+  return verify_lists("refine", W.s, W.n, G, true, err);
 }
 
 // Steps 2 and 3 for one block of results (device pointers): G -> out.
-int merge_block(Work& W, const Graph& G, Results R, bool with_incoming, Graph& out) {
+int merge_block(Work& W, const DeviceGraph& G, Results R, bool with_incoming, DeviceGraph& out) {
   const uint32_t n = W.n, m = R.count + 1;
   hipStream_t s = W.s;
   uint32_t words[kWords];
@@ -132,7 +75,7 @@ int merge_block(Work& W, const Graph& G, Results R, bool with_incoming, Graph& o
   HIP_OK(hipGetLastError());
   uint64_t total = 0;
   HIP_OK(hipMemcpyAsync(&total, W.boff.p + m, 8, hipMemcpyDeviceToHost, s));
-  if (fetch(W, words, W.words.p, kWords)) return -1;
+  if (fetch(s, words, W.words.p, kWords)) return -1;
   if (words[kErrResultCount] != kNone)
     return fail("refine: query %u has more results than the stride %u", words[kErrResultCount], R.stride);
   if (words[kErrResultId] != kNone)
@@ -159,7 +102,7 @@ int merge_block(Work& W, const Graph& G, Results R, bool with_incoming, Graph& o
     HIP_OK(hipGetLastError());
     uint64_t C = 0;
     HIP_OK(hipMemcpyAsync(&C, W.coff.p + n, 8, hipMemcpyDeviceToHost, s));
-    if (fetch(W, words, W.words.p, kWords)) return -1;
+    if (fetch(s, words, W.words.p, kWords)) return -1;
     HIP_OK(W.cka.alloc(C));
     HIP_OK(W.ckb.alloc(C));
     HIP_OK(W.cx.alloc(C));
@@ -178,7 +121,7 @@ int merge_block(Work& W, const Graph& G, Results R, bool with_incoming, Graph& o
   max_u32(W.nlen.p, n, W.words.p + kWordNewLen, s);
   HIP_OK(hipGetLastError());
   HIP_OK(hipMemcpyAsync(&out.edges, W.noff.p + n, 8, hipMemcpyDeviceToHost, s));
-  if (fetch(W, words, W.words.p, kWords)) return -1;
+  if (fetch(s, words, W.words.p, kWords)) return -1;
   out.maxlen = words[kWordNewLen];
   HIP_OK(out.off.alloc((size_t)n + 1));
   HIP_OK(out.ids.alloc(out.edges));
@@ -190,7 +133,7 @@ int merge_block(Work& W, const Graph& G, Results R, bool with_incoming, Graph& o
   return 0;
 }
 
-int prune(Work& W, const Graph& G, uint32_t k, Graph& out) {
+int prune(Work& W, const DeviceGraph& G, uint32_t k, DeviceGraph& out) {
   const uint32_t n = W.n;
   hipStream_t s = W.s;
   HIP_OK(W.words.alloc(kWords));
@@ -203,7 +146,7 @@ int prune(Work& W, const Graph& G, uint32_t k, Graph& out) {
   HIP_OK(hipGetLastError());
   uint32_t words[kWords];
   HIP_OK(hipMemcpyAsync(&out.edges, out.off.p + n, 8, hipMemcpyDeviceToHost, s));
-  if (fetch(W, words, W.words.p, kWords)) return -1;
+  if (fetch(s, words, W.words.p, kWords)) return -1;
   out.maxlen = words[kWordNewLen];
   HIP_OK(out.ids.alloc(out.edges));
   HIP_OK(out.d.alloc(out.edges));
@@ -213,44 +156,16 @@ int prune(Work& W, const Graph& G, uint32_t k, Graph& out) {
   return 0;
 }
 
-struct Result {
-  std::vector<uint64_t> off;
-  std::vector<uint32_t> ids;
-  std::vector<float> d;
-  ngt_amd_refine_stats stats{};
-  bool ready = false;
-};
-thread_local Result t_result;
+thread_local HostGraph t_graph;
+thread_local ngt_amd_refine_stats t_stats;
 
-int download(Work& W, const Graph& G, Result& res) {
-  const uint32_t n = W.n;
-  res.off.resize((size_t)n + 1);
-  res.ids.resize(G.edges);
-  res.d.resize(G.edges);
-  HIP_OK(hipMemcpyAsync(res.off.data(), G.off.p, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, W.s));
-  if (G.edges) HIP_OK(hipMemcpyAsync(res.ids.data(), G.ids.p, G.edges * 4, hipMemcpyDeviceToHost, W.s));
-  if (G.edges) HIP_OK(hipMemcpyAsync(res.d.data(), G.d.p, G.edges * 4, hipMemcpyDeviceToHost, W.s));
-  HIP_OK(hipStreamSynchronize(W.s));
+// G and the run's counters into the thread's result
+int finish(Work& W, const DeviceGraph& G, HostGraph& res, ngt_amd_refine_stats& stats) {
+  if (download_graph(W.s, W.n, G, res)) return -1;
   W.st.edges_out = G.edges;
   W.st.longest_list = G.maxlen;
-  res.stats = W.st;
+  stats = W.st;
   res.ready = true;
-  return 0;
-}
-
-struct Stream {
-  hipStream_t s = nullptr;
-  ~Stream() {
-    if (s) (void)hipStreamDestroy(s);
-  }
-};
-
-int select_device(const char* who, int device) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-    return fail("%s: no HIP device available (the MI355X path has no CPU fallback)", who);
-  if (device < 0 || device >= ndev) return fail("%s: device %d out of range", who, device);
-  HIP_OK(hipSetDevice(device));
   return 0;
 }
 
@@ -258,16 +173,10 @@ int select_device(const char* who, int device) {
 // Points the index's CSR ids at G (not owned) and refreshes the padded copy,
 // the widest list and adj_version; `es` is the resolved edge size of the
 // refinement's searches.
-int point_index_at(ngt_amd_index* ix, const Graph& G, uint64_t es, hipStream_t s) {
+int point_index_at(ngt_amd_index* ix, const DeviceGraph& G, uint64_t es, hipStream_t s) {
   std::lock_guard<std::mutex> lk(ix->mu);
-  ix->edge_off.release();
-  ix->edge_off.p = G.off.p;
-  ix->edge_off.n = ix->nrows + 1;
-  ix->edge_off.owned = false;
-  ix->edges.release();
-  ix->edges.p = G.ids.p;
-  ix->edges.n = G.edges;
-  ix->edges.owned = false;
+  ix->edge_off.borrow(G.off.p, ix->nrows + 1);
+  ix->edges.borrow(G.ids.p, G.edges);
   ix->nedges = G.edges;
   ix->has_graph = true;
   ix->max_degree = G.maxlen;
@@ -317,10 +226,10 @@ double seconds_since(std::chrono::steady_clock::time_point t0) {
 }
 
 int refine_index(ngt_amd_index* ix, const uint64_t* offsets, const uint32_t* ids, const float* dists,
-                 const ngt_amd_refine_params& p, Result& res) {
+                 const ngt_amd_refine_params& p, HostGraph& res, ngt_amd_refine_stats& stats) {
   res.ready = false;
   uint32_t longest = 0;
-  if (check_csr("ngt_amd_refine_anng", offsets, ids, dists, ix->nrows, &longest)) return -1;
+  if (check_csr("ngt_amd_refine_anng", offsets, ids, dists, ix->nrows, true, &longest)) return -1;
   if (!ix->rows.p || ix->nrows < 2) return fail("ngt_amd_refine_anng: the index has no objects");
   if (!ix->has_tree) return fail("ngt_amd_refine_anng: the index has no tree (the searches take their seeds from it)");
   if (p.batch_size == 0) return fail("ngt_amd_refine_anng: the batch size is 0");
@@ -344,9 +253,8 @@ int refine_index(ngt_amd_index* ix, const uint64_t* offsets, const uint32_t* ids
   W.n = (uint32_t)ix->nrows;
   const uint32_t n = W.n;
   W.st.edges_in = offsets[n];
-  Graph cur, next;
-  if (upload_graph(W, offsets, ids, dists, cur)) return -1;
-  cur.maxlen = longest;
+  DeviceGraph cur, next;
+  if (upload_lists(W, offsets, ids, dists, longest, cur)) return -1;
   GraphGuard guard{ix, offsets, ids};
   guard.armed = true;
   if (point_index_at(ix, cur, es, W.s)) return -1;
@@ -358,14 +266,8 @@ int refine_index(ngt_amd_index* ix, const uint64_t* offsets, const uint32_t* ids
   HIP_OK(rid.alloc((size_t)B * size));
   HIP_OK(rd.alloc((size_t)B * size));
   HIP_OK(rn.alloc(B));
-  ngt_amd_search_params sp{};
-  sp.k = size;
-  sp.epsilon = p.epsilon;
-  sp.radius = FLT_MAX;
-  sp.edge_size = p.explore_edge_size;
-  sp.seed_mode = NGT_AMD_SEED_TREE;
-  sp.all_leaf_nodes = 0;
-  sp.visited_hash_log2 = ix->nrows >= (1u << 18) ? -1 : 0;  // as ngt_search_index
+  const ngt_amd_search_params sp =
+      library_search_params(ix->nrows, size, p.epsilon, FLT_MAX, p.explore_edge_size, NGT_AMD_SEED_TREE);
   for (uint64_t bid = 1; bid < n; bid += B) {
     const uint32_t count = (uint32_t)std::min<uint64_t>(B, n - bid);
     auto t0 = std::chrono::steady_clock::now();
@@ -400,19 +302,17 @@ int refine_index(ngt_amd_index* ix, const uint64_t* offsets, const uint32_t* ids
     HIP_OK(hipStreamSynchronize(W.s));
     W.st.merge_ms += seconds_since(t0) * 1e3;
   }
-  if (download(W, cur, res)) return -1;
+  if (finish(W, cur, res, stats)) return -1;
   // the index owns the final CSR from here on
   {
     std::lock_guard<std::mutex> lk(ix->mu);
-    ix->edge_off.owned = true;
-    ix->edges.owned = true;
-    cur.off.p = nullptr;
-    cur.ids.p = nullptr;
+    ix->edge_off.take_from(cur.off);
+    ix->edges.take_from(cur.ids);
     ix->h_graph_empty.assign(n, 1);
     for (uint32_t v = 0; v < n; v++) ix->h_graph_empty[v] = res.off[v + 1] == res.off[v];
   }
   guard.armed = false;
-  res.stats.total_ms = seconds_since(t_all) * 1e3;
+  stats.total_ms = seconds_since(t_all) * 1e3;
   return 0;
 }
 
@@ -426,23 +326,22 @@ extern "C" int ngt_amd_refine_merge(int device, const uint64_t* offsets, const u
                                     int incoming, uint64_t* out_nedges) {
   if (!out_nedges) return fail("ngt_amd_refine_merge: bad arguments");
   *out_nedges = 0;
-  t_result = Result();
+  t_graph = HostGraph();
   uint32_t longest = 0;
-  if (check_csr("ngt_amd_refine_merge", offsets, ids, dists, nrows, &longest)) return -1;
+  if (check_csr("ngt_amd_refine_merge", offsets, ids, dists, nrows, true, &longest)) return -1;
   if (first_id < 1 || first_id >= nrows) return fail("ngt_amd_refine_merge: first id %u outside [1, %llu)", first_id, (unsigned long long)nrows);
   if (count && (!res_counts || (stride && (!res_ids || !res_dists)))) return fail("ngt_amd_refine_merge: bad arguments");
   // a last batch overhangs the rows: its tail holds no object
   const uint32_t used = (uint32_t)std::min<uint64_t>(count, nrows - first_id);
   if (select_device("ngt_amd_refine_merge", device)) return -1;
-  Stream st;
-  HIP_OK(hipStreamCreateWithFlags(&st.s, hipStreamDefault));
+  OwnedStream st;
+  if (st.create()) return -1;
   Work W;
   W.s = st.s;
   W.n = (uint32_t)nrows;
   W.st.edges_in = offsets[nrows];
-  Graph G, out;
-  if (upload_graph(W, offsets, ids, dists, G)) return -1;
-  G.maxlen = longest;
+  DeviceGraph G, out;
+  if (upload_lists(W, offsets, ids, dists, longest, G)) return -1;
   DevBuf<uint32_t> rid, rn;
   DevBuf<float> rd;
   const size_t slots = (size_t)used * stride;
@@ -456,11 +355,11 @@ extern "C" int ngt_amd_refine_merge(int device, const uint64_t* offsets, const u
   if (merge_block(W, G, R, incoming != 0, out)) return -1;
   W.st.batches = 1;
   W.st.searched = used;
-  if (download(W, out, t_result)) {
-    t_result = Result();
+  if (finish(W, out, t_graph, t_stats)) {
+    t_graph = HostGraph();
     return -1;
   }
-  *out_nedges = t_result.ids.size();
+  *out_nedges = t_graph.ids.size();
   return 0;
 }
 
@@ -468,24 +367,24 @@ extern "C" int ngt_amd_refine_prune(int device, const uint64_t* offsets, const u
                                     uint64_t nrows, uint32_t num_edges, uint64_t* out_nedges) {
   if (!out_nedges) return fail("ngt_amd_refine_prune: bad arguments");
   *out_nedges = 0;
-  t_result = Result();
+  t_graph = HostGraph();
   uint32_t longest = 0;
-  if (check_csr("ngt_amd_refine_prune", offsets, ids, dists, nrows, &longest)) return -1;
+  if (check_csr("ngt_amd_refine_prune", offsets, ids, dists, nrows, true, &longest)) return -1;
   if (select_device("ngt_amd_refine_prune", device)) return -1;
-  Stream st;
-  HIP_OK(hipStreamCreateWithFlags(&st.s, hipStreamDefault));
+  OwnedStream st;
+  if (st.create()) return -1;
   Work W;
   W.s = st.s;
   W.n = (uint32_t)nrows;
   W.st.edges_in = offsets[nrows];
-  Graph G, out;
-  if (upload_graph(W, offsets, ids, dists, G)) return -1;
+  DeviceGraph G, out;
+  if (upload_lists(W, offsets, ids, dists, longest, G)) return -1;
   if (prune(W, G, num_edges, out)) return -1;
-  if (download(W, out, t_result)) {
-    t_result = Result();
+  if (finish(W, out, t_graph, t_stats)) {
+    t_graph = HostGraph();
     return -1;
   }
-  *out_nedges = t_result.ids.size();
+  *out_nedges = t_graph.ids.size();
   return 0;
 }
 
@@ -494,30 +393,25 @@ extern "C" int ngt_amd_refine_anng(ngt_amd_index* ix, const uint64_t* offsets, c
                                    uint64_t* out_nedges) {
   if (!ix || !params || !out_nedges) return fail("ngt_amd_refine_anng: bad arguments");
   *out_nedges = 0;
-  t_result = Result();
+  t_graph = HostGraph();
   if (nrows != ix->nrows)
     return fail("ngt_amd_refine_anng: the graph has %llu rows, the index %llu", (unsigned long long)nrows,
                 (unsigned long long)ix->nrows);
-  if (refine_index(ix, offsets, ids, dists, *params, t_result)) {
-    t_result = Result();
+  if (refine_index(ix, offsets, ids, dists, *params, t_graph, t_stats)) {
+    t_graph = HostGraph();
     return -1;
   }
-  *out_nedges = t_result.ids.size();
+  *out_nedges = t_graph.ids.size();
   return 0;
 }
 
 extern "C" int ngt_amd_refine_get_graph(uint64_t* offsets, uint32_t* ids, float* dists) {
-  if (!t_result.ready) return fail("ngt_amd_refine_get_graph: no refined graph on this thread");
-  if (!offsets) return fail("ngt_amd_refine_get_graph: bad arguments");
-  memcpy(offsets, t_result.off.data(), t_result.off.size() * 8);
-  if (ids && !t_result.ids.empty()) memcpy(ids, t_result.ids.data(), t_result.ids.size() * 4);
-  if (dists && !t_result.d.empty()) memcpy(dists, t_result.d.data(), t_result.d.size() * 4);
-  return 0;
+  return copy_out(t_graph, "ngt_amd_refine_get_graph", "refined", offsets, ids, dists);
 }
 
 extern "C" int ngt_amd_refine_last_stats(ngt_amd_refine_stats* stats) {
   if (!stats) return fail("ngt_amd_refine_last_stats: bad arguments");
-  if (!t_result.ready) return fail("ngt_amd_refine_last_stats: no refined graph on this thread");
-  *stats = t_result.stats;
+  if (!t_graph.ready) return fail("ngt_amd_refine_last_stats: no refined graph on this thread");
+  *stats = t_stats;
   return 0;
 }

@@ -3,9 +3,8 @@ include/ngt_amd.h (edge and path adjustment of GraphOptimizer::execute) on a
 host CSR graph."""
 import ctypes
 
-import numpy as np
-
 from . import NativeError, _sigs, last_error, lib
+from ._csr import as_csr, take_graph
 
 
 def fast_path_capacity():
@@ -18,22 +17,14 @@ def reconstruct(offsets, ids, dists, outgoing, incoming, path_adjustment, min_ed
     """Returns the new (offsets uint64, ids uint32, dists float32); with
     ``with_stats`` also the stage times and counters as a dict."""
     L = lib()
-    off = np.ascontiguousarray(offsets, dtype=np.uint64)
-    i = np.ascontiguousarray(ids, dtype=np.uint32)
-    d = np.ascontiguousarray(dists, dtype=np.float32)
-    if len(off) < 1 or len(i) != len(d) or int(off[-1]) != len(i):
-        raise NativeError("onng.reconstruct: offsets, ids and dists do not describe one CSR graph")
+    off, i, d = as_csr(offsets, ids, dists, "onng.reconstruct", 1)
     p = _sigs.OnngParams(int(outgoing), int(incoming), int(bool(path_adjustment)), int(bool(input_is_anng)),
                          int(min_edges))
     ne = ctypes.c_uint64(0)
     if L.ngt_amd_onng_reconstruct(int(device), off.ctypes.data, i.ctypes.data, d.ctypes.data, len(off) - 1,
                                   ctypes.byref(p), ctypes.byref(ne)):
         raise NativeError(last_error())
-    o2 = np.zeros(len(off), np.uint64)
-    i2 = np.zeros(ne.value, np.uint32)
-    d2 = np.zeros(ne.value, np.float32)
-    if L.ngt_amd_onng_get_graph(o2.ctypes.data, i2.ctypes.data, d2.ctypes.data):
-        raise NativeError(last_error())
+    o2, i2, d2 = take_graph(L.ngt_amd_onng_get_graph, len(off) - 1, ne.value)
     if not with_stats:
         return o2, i2, d2
     st = _sigs.OnngStats()

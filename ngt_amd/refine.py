@@ -6,6 +6,7 @@ import ctypes
 import numpy as np
 
 from . import NativeError, _sigs, last_error, lib
+from ._csr import as_csr, take_graph
 
 
 def fast_path_capacity():
@@ -13,22 +14,9 @@ def fast_path_capacity():
     return int(lib().ngt_amd_refine_fast_path_capacity())
 
 
-def _csr(offsets, ids, dists, who):
-    off = np.ascontiguousarray(offsets, dtype=np.uint64)
-    i = np.ascontiguousarray(ids, dtype=np.uint32)
-    d = np.ascontiguousarray(dists, dtype=np.float32)
-    if len(off) < 2 or len(i) != len(d) or int(off[-1]) != len(i):
-        raise NativeError("refine.%s: offsets, ids and dists do not describe one CSR graph" % who)
-    return off, i, d
-
-
 def _result(nrows, nedges, with_stats):
     L = lib()
-    o2 = np.zeros(nrows + 1, np.uint64)
-    i2 = np.zeros(nedges, np.uint32)
-    d2 = np.zeros(nedges, np.float32)
-    if L.ngt_amd_refine_get_graph(o2.ctypes.data, i2.ctypes.data, d2.ctypes.data):
-        raise NativeError(last_error())
+    o2, i2, d2 = take_graph(L.ngt_amd_refine_get_graph, nrows, nedges)
     if not with_stats:
         return o2, i2, d2
     st = _sigs.RefineStats()
@@ -41,7 +29,7 @@ def merge(offsets, ids, dists, first_id, res_ids, res_dists, res_counts, incomin
     """The outgoing step (and the incoming step when ``incoming``) for one block
     of results: query q is node first_id + q with results res_ids/res_dists[q,
     :res_counts[q]].  Returns the new (offsets uint64, ids uint32, dists float32)."""
-    off, i, d = _csr(offsets, ids, dists, "merge")
+    off, i, d = as_csr(offsets, ids, dists, "refine.merge", 2)
     ri = np.ascontiguousarray(res_ids, dtype=np.uint32)
     rd = np.ascontiguousarray(res_dists, dtype=np.float32)
     rn = np.ascontiguousarray(res_counts, dtype=np.uint32)
@@ -57,7 +45,7 @@ def merge(offsets, ids, dists, first_id, res_ids, res_dists, res_counts, incomin
 
 def prune(offsets, ids, dists, num_edges, device=0):
     """Every list longer than num_edges cut to num_edges."""
-    off, i, d = _csr(offsets, ids, dists, "prune")
+    off, i, d = as_csr(offsets, ids, dists, "refine.prune", 2)
     ne = ctypes.c_uint64(0)
     if lib().ngt_amd_refine_prune(int(device), off.ctypes.data, i.ctypes.data, d.ctypes.data, len(off) - 1,
                                   int(num_edges), ctypes.byref(ne)):
@@ -70,7 +58,7 @@ def refine_anng(index, offsets, ids, dists, epsilon, num_edges, edge_size_for_cr
     """The whole refinement on a ``DeviceIndex`` that has rows and a tree;
     offsets/ids/dists is its graph with distances.  Afterwards the index
     searches the refined graph, which is returned."""
-    off, i, d = _csr(offsets, ids, dists, "refine_anng")
+    off, i, d = as_csr(offsets, ids, dists, "refine.refine_anng", 2)
     p = _sigs.RefineParams(float(epsilon), int(num_edges), int(explore_edge_size), int(batch_size),
                            int(edge_size_for_creation), 0)
     ne = ctypes.c_uint64(0)

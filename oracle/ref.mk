@@ -37,14 +37,14 @@ $(OUT)/libngt_ref.so: $(OBJS)
 	$(CXX) -shared -fopenmp -o $@ $(OBJS) -lrt
 
 $(OUT)/ngt: $(REF)/bin/ngt/ngt.cpp $(OUT)/libngt_ref.so
-	$(CXX) $(CXXFLAGS) -o $@ $< -L$(OUT) -lngt_ref -Wl,-rpath,$(abspath $(OUT))
+	$(CXX) $(CXXFLAGS) -o $@ $< -L$(OUT) -lngt_ref -Wl,-rpath,'$$ORIGIN'
 
 $(OUT)/ngtqg: $(REF)/bin/ngtqg/ngtqg.cpp $(OUT)/libngt_ref.so
-	$(CXX) $(CXXFLAGS) -o $@ $< -L$(OUT) -lngt_ref -Wl,-rpath,$(abspath $(OUT))
+	$(CXX) $(CXXFLAGS) -o $@ $< -L$(OUT) -lngt_ref -Wl,-rpath,'$$ORIGIN'
 
 # fixture harnesses (committed under tests/golden/, compiled against the reference headers)
 $(OUT)/qg_harness: tests/golden/qg_harness.cpp $(OUT)/libngt_ref.so
-	$(CXX) $(CXXFLAGS) -o $@ $< -L$(OUT) -lngt_ref -Wl,-rpath,$(abspath $(OUT))
+	$(CXX) $(CXXFLAGS) -o $@ $< -L$(OUT) -lngt_ref -Wl,-rpath,'$$ORIGIN'
 
 $(OUT)/comparator_harness: tests/golden/comparator_harness.cpp $(GEN)/NGT/defines.h
 	$(CXX) $(CXXFLAGS) -o $@ $<
@@ -53,13 +53,13 @@ clean:
 	rm -rf $(OUT)
 
 $(OUT)/ngtq: $(REF)/bin/ngtq/ngtq.cpp $(OUT)/libngt_ref.so
-	$(CXX) $(CXXFLAGS) -o $@ $< -L$(OUT) -lngt_ref -Wl,-rpath,$(abspath $(OUT))
+	$(CXX) $(CXXFLAGS) -o $@ $< -L$(OUT) -lngt_ref -Wl,-rpath,'$$ORIGIN'
 
 $(OUT)/ngtq_harness: tests/golden/ngtq_harness.cpp $(OUT)/libngt_ref.so
-	$(CXX) $(CXXFLAGS) -o $@ $< -L$(OUT) -lngt_ref -Wl,-rpath,$(abspath $(OUT))
+	$(CXX) $(CXXFLAGS) -o $@ $< -L$(OUT) -lngt_ref -Wl,-rpath,'$$ORIGIN'
 
 $(OUT)/kmeans_harness: tests/golden/kmeans_harness.cpp ngt_amd/csrc/kmeans_ngt.h $(OUT)/libngt_ref.so
-	$(CXX) $(CXXFLAGS) -Ingt_amd/csrc -o $@ $< -L$(OUT) -lngt_ref -Wl,-rpath,$(abspath $(OUT))
+	$(CXX) $(CXXFLAGS) -Ingt_amd/csrc -o $@ $< -L$(OUT) -lngt_ref -Wl,-rpath,'$$ORIGIN'
 
 $(OUT)/accuracy_harness: tests/golden/accuracy_harness.cpp $(OUT)/libngt_ref.so
-	$(CXX) $(CXXFLAGS) -o $@ $< -L$(OUT) -lngt_ref -Wl,-rpath,$(abspath $(OUT))
+	$(CXX) $(CXXFLAGS) -o $@ $< -L$(OUT) -lngt_ref -Wl,-rpath,'$$ORIGIN'

@@ -256,3 +256,62 @@ def test_ngtpy_and_cxx_facade(sources, tmp_path):
     assert r.returncode == 0, r.stderr
     assert CASES["A"]["line"] in r.stdout.splitlines()
     assert read(idx, "prf").decode() == CASES["A"]["prf"]
+
+
+# ---- the thread-local result slots -------------------------------------------------
+def in_fresh_thread(f):
+    """f() on a new thread, whose result slots start empty; its return value or its exception."""
+    import threading
+    out = []
+
+    def body():
+        try:
+            out.append((f(), None))
+        except BaseException as e:  # noqa: BLE001 -- handed to the caller's thread
+            out.append((None, e))
+
+    t = threading.Thread(target=body)
+    t.start()
+    t.join()
+    if out[0][1] is not None:
+        raise out[0][1]
+    return out[0][0]
+
+
+def ask(getter):
+    """(status, message) of a *_get_graph entry point, and the 3-row graph it returned."""
+    off, ids, ds = np.zeros(4, np.uint64), np.zeros(16, np.uint32), np.zeros(16, np.float32)
+    r = getattr(ngt_amd.lib(), getter)(off.ctypes.data, ids.ctypes.data, ds.ctypes.data)
+    return r, (ngt_amd.last_error() if r else ""), (off, ids[:int(off[-1])], ds[:int(off[-1])])
+
+
+def test_a_recut_fills_its_own_result_slot_alone():
+    off, ids, ds = csr([[], [(2, 1.0)], [(1, 1.0)]])
+
+    def body():
+        got = edges.recut(off, ids, ds, 5)
+        return got, ask("ngt_amd_onng_get_graph"), ask("ngt_amd_refine_get_graph"), ask("ngt_amd_recut_get_graph")
+
+    got, o, r, e = in_fresh_thread(body)
+    assert o[:2] == (-1, "ngt_amd_onng_get_graph: no reconstructed graph on this thread")
+    assert r[:2] == (-1, "ngt_amd_refine_get_graph: no refined graph on this thread")
+    assert e[:2] == (0, "")
+    want = D.recut(off, ids, ds, 5)
+    for a, b, c in zip(e[2], got, want):
+        assert np.array_equal(a, b) and np.array_equal(a, c)
+    assert np.array_equal(e[2][2].view(np.uint32), want[2].view(np.uint32))
+
+
+def test_a_failed_reconstruction_clears_its_slot():
+    off, ids, ds = csr([[], [(2, 1.0)], [(1, 1.0)]])
+
+    def body():
+        onng.reconstruct(off, ids, ds, 1, 1, False)
+        first = ask("ngt_amd_onng_get_graph")
+        with pytest.raises(ngt_amd.NativeError, match=r"holds an id outside \[1, 3\)"):
+            onng.reconstruct(off, np.array([3, 1], np.uint32), ds, 1, 1, False)
+        return first, ask("ngt_amd_onng_get_graph")
+
+    first, second = in_fresh_thread(body)
+    assert first[:2] == (0, "")
+    assert second[:2] == (-1, "ngt_amd_onng_get_graph: no reconstructed graph on this thread")
