@@ -232,17 +232,47 @@ uint32_t ngt_amd_last_search_budget(const ngt_amd_index *index);
  *   (Graph.h:611-625) and DVPTree::insert (Tree.cpp:27-265).  The objects must
  *   be set first (ngt_amd_index_set_objects); the index's search graph is
  *   replaced by the construction's padded adjacency until the built graph is
- *   set back with ngt_amd_index_set_graph. */
+ *   set back with ngt_amd_index_set_graph.
+ *
+ *   graph_type selects the insertion rule (NeighborhoodGraph::insertNode,
+ *   Graph.h:533-562); 0 means ANNG, so a zeroed field keeps its old meaning.
+ *   - IANNG: the ANNG's searches and merge, then insertIANNGNode
+ *     (Graph.h:628-635, addEdgeDeletingExcessEdges :888-934).  Equal to the
+ *     reference at any creation thread count.
+ *   - ONNG: the same, then insertONNGNode (Graph.h:637-655): reverse edges for
+ *     the first incoming_edge results, the stored list cut to outgoing_edge
+ *     afterwards (ngt_amd_build_set_onng_edges; 10 and 80 by default).  Equal
+ *     to the reference at any creation thread count.
+ *   - KNNG: no insertion search.  Each object's list is its exact
+ *     edge_size_for_creation + 1 nearest among all stored objects
+ *     (searchForKNNGInsertion, Index.h:839-856) -- ngt_amd_linear_search_device
+ *     with the stored rows as queries -- after ObjectDistances::moveFrom
+ *     (ObjectSpace.h:70-88): the object itself leaves the list, or, when more
+ *     than edge_size_for_creation duplicates with smaller ids kept it out, the
+ *     nearest entry does (the reference's release build; its debug build
+ *     asserts there).  No reverse edges; a list never changes afterwards.  The
+ *     DVP tree takes the objects in id order, which is the reference run with
+ *     one creation thread (ngt create -p 1): with more threads its KNNG tree
+ *     follows thread completion order.  edge_size_for_creation + 1 must be a k
+ *     the linear search accepts; beyond that ngt_amd_build_insert fails with
+ *     that function's message before the session's graph or tree change.
+ *   BKNNG and DNNG are refused. */
+#define NGT_AMD_GRAPH_ANNG 1
+#define NGT_AMD_GRAPH_KNNG 2
+#define NGT_AMD_GRAPH_ONNG 4
+#define NGT_AMD_GRAPH_IANNG 5
 typedef struct {
   int32_t edge_size_for_creation;   /* EdgeSizeForCreation (10)                      */
   int32_t edge_size_for_search;     /* EdgeSizeForSearch (40), <= 256; 0 = all edges */
   int32_t batch_size_for_creation;  /* BatchSizeForCreation (200)                    */
   int32_t seed_size;                /* SeedSize (10)                                 */
   float epsilon_for_creation;       /* EpsilonForCreation (0.1)                      */
-  int32_t reserved;
+  int32_t graph_type;               /* NGT_AMD_GRAPH_*; 0 = ANNG                     */
 } ngt_amd_build_params;
 
 int ngt_amd_build_begin(ngt_amd_index *index, const ngt_amd_build_params *params);
+/* OutgoingEdge / IncomingEdge of an ONNG session (after ngt_amd_build_begin). */
+int ngt_amd_build_set_onng_edges(ngt_amd_index *index, int32_t outgoing_edge, int32_t incoming_edge);
 /* Insert the valid objects with ids in [first_id, end_id) not yet in the graph. */
 int ngt_amd_build_insert(ngt_amd_index *index, uint64_t first_id, uint64_t end_id);
 /* GraphRepository size (max inserted id + 1) and total edge count. */

@@ -21,7 +21,7 @@ class NgtqSearchParams(Structure):
 class BuildParams(Structure):
     _fields_ = [("edge_size_for_creation", c_int32), ("edge_size_for_search", c_int32),
                 ("batch_size_for_creation", c_int32), ("seed_size", c_int32), ("epsilon_for_creation", c_float),
-                ("reserved", c_int32)]
+                ("graph_type", c_int32)]  # GRAPH_* of device.py; 0 = ANNG
 
 
 class OnngParams(Structure):
@@ -128,6 +128,7 @@ def declare(L):
         "ngt_amd_last_search_budget": (c_uint32, [vp]),
         "ngt_amd_last_search_filtered": (c_int, [vp]),
         "ngt_amd_build_begin": (c_int, [vp, POINTER(BuildParams)]),
+        "ngt_amd_build_set_onng_edges": (c_int, [vp, c_int32, c_int32]),
         "ngt_amd_build_insert": (c_int, [vp, c_uint64, c_uint64]),
         "ngt_amd_build_graph_size": (c_int, [vp, u64p, u64p]),
         "ngt_amd_build_get_graph": (c_int, [vp, vp, vp, vp]),

@@ -1,6 +1,7 @@
-// build.cpp -- ANNG construction on the MI355X:
+// build.cpp -- graph construction on the MI355X:
 // GraphAndTreeIndex::createIndex(threadPoolSize) (lib/NGT/Index.cpp:1158-1257)
-// for graphType ANNG with the default (disabled) edge truncation.
+// for graphType ANNG, IANNG, ONNG and KNNG with the default (disabled) edge
+// truncation.  The ANNG first; the other types follow below.
 //
 // Per creation batch of batchSizeForCreation objects, in id order
 // (searchMultipleQueryForCreation, Index.cpp:631-671):
@@ -20,6 +21,43 @@
 // The graph being built is host-side (sorted edge lists, the reference's
 // GraphRepository); the insertion searches read a padded HBM copy of each
 // node's first edgeSizeForSearch edges, refreshed for the nodes a batch touched.
+//
+// IANNG and ONNG keep steps 1, 2 and 4 and the merge of step 3; only the
+// insertion rule differs (NeighborhoodGraph::insertNode, Graph.h:533-562):
+//   IANNG  insertIANNGNode (Graph.h:628-635): every reverse edge goes through
+//          addEdgeDeletingExcessEdges (:888-934), which first drops the target's
+//          edge at rank edgeSizeForCreation - 1, in both directions, when that
+//          edge is not shorter than the new one and the node it leads to also
+//          has one at that rank that is not longer;
+//   ONNG   insertONNGNode (Graph.h:637-655): reverse edges for the first
+//          incomingEdge results, the stored list cut to outgoingEdge afterwards.
+// Both equal the reference at any creation thread count: it sorts a batch's
+// jobs by their place in the batch before it merges and inserts them
+// (Index.cpp:676-703).
+//
+// KNNG (insertKNNGNode, Graph.h:607-609) has no insertion search, no in-batch
+// distances and no reverse edges.  Per batch:
+//   a. the batch objects' exact edgeSizeForCreation + 1 nearest among all the
+//      stored objects (searchForKNNGInsertion, Index.h:839-856: linearSearch
+//      over the object repository as it stands, radius FLT_MAX) -- the
+//      library's exact scan, ngt_amd_linear_search_device, with the stored rows
+//      as the prepared queries, read where they lie in HBM; the validity flags
+//      hide removed rows.  edgeSizeForCreation + 1 is therefore limited to a k
+//      that function accepts: beyond it the call fails with that function's
+//      message before the session's graph or tree change;
+//   b. ngt_knng_lists_kernel: ObjectDistances::moveFrom (ObjectSpace.h:70-88)
+//      -- the object itself leaves its list, or, when more than
+//      edgeSizeForCreation exact duplicates with smaller ids kept it out of its
+//      own E + 1 nearest, the nearest entry does (what the reference's release
+//      build does; its debug build asserts there) -- written to the session's
+//      lists and to the padded adjacency, with the tree-insertion flag;
+//   c. DVPTree::insert of the batch in id order.  That is the reference run
+//      with one creation thread: with more, its KNNG jobs reach the tree in
+//      thread completion order (only the other types' are sorted) and its tre
+//      does not repeat.
+// The lists depend on neither the batch size nor the thread count, and a list
+// never changes after its node's insertion; they make one trip to the host, for
+// the graph mirror.
 #include <hip/hip_runtime.h>
 #include <float.h>
 #include <math.h>
@@ -104,6 +142,11 @@ extern "C" int ngt_amd_build_begin(ngt_amd_index* ix, const ngt_amd_build_params
   b->batch_size = prm->batch_size_for_creation;
   b->seed_size = prm->seed_size;
   b->epsilon_for_creation = prm->epsilon_for_creation;
+  b->graph_type = prm->graph_type == 0 ? NGT_AMD_GRAPH_ANNG : prm->graph_type;
+  if (b->graph_type != NGT_AMD_GRAPH_ANNG && b->graph_type != NGT_AMD_GRAPH_KNNG &&
+      b->graph_type != NGT_AMD_GRAPH_ONNG && b->graph_type != NGT_AMD_GRAPH_IANNG)
+    return fail("ngt_amd_build_begin: graph type %d unsupported (ANNG 1, KNNG 2, ONNG 4 and IANNG 5 are built)",
+                prm->graph_type);
   b->graph.assign(ix->nrows, {});
   b->in_graph.assign(ix->nrows, 0);
   b->rnd.seed(1);
@@ -132,6 +175,200 @@ extern "C" int ngt_amd_build_begin(ngt_amd_index* ix, const ngt_amd_build_params
   return 0;
 }
 
+extern "C" int ngt_amd_build_set_onng_edges(ngt_amd_index* ix, int32_t outgoing_edge, int32_t incoming_edge) {
+  if (!ix || !ix->build) return fail("ngt_amd_build_set_onng_edges: call ngt_amd_build_begin first");
+  if (outgoing_edge < 1 || incoming_edge < 0)
+    return fail("ngt_amd_build_set_onng_edges: outgoing_edge %d must be >= 1 and incoming_edge %d >= 0",
+                outgoing_edge, incoming_edge);
+  ix->build->outgoing_edge = outgoing_edge;
+  ix->build->incoming_edge = incoming_edge;
+  return 0;
+}
+
+namespace {
+
+// the tree fields of a batch's DVPTree::insert launch; the caller adds the
+// pre-located leaves, if it has them
+TreeBuildArgs tree_insert_args(ngt_amd_index* ix, BuildState& b, const uint32_t* d_ids, const uint8_t* d_flag,
+                               uint32_t n) {
+  TreeBuildArgs ta{};
+  ta.rows = ix->rows.p;
+  ta.row_bytes = ix->row_bytes;
+  ta.dp = (int)ix->dp;
+  ta.lf_parent = b.lf_parent.p;
+  ta.lf_has_pivot = b.lf_has_pivot.p;
+  ta.lf_pivot = b.lf_pivot.p;
+  ta.lf_count = b.lf_count.p;
+  ta.lf_ids = b.lf_ids.p;
+  ta.lf_dist = b.lf_dist.p;
+  ta.leaf_cap = kLeafCap;
+  ta.in_parent = b.in_parent.p;
+  ta.in_pivot = b.in_pivot.p;
+  ta.in_child = b.in_child.p;
+  ta.in_border = b.in_border.p;
+  ta.counts = b.counts.p;
+  ta.leaf_cap_nodes = b.leaf_cap_nodes;
+  ta.in_cap_nodes = b.in_cap_nodes;
+  ta.leaf_size = 100;  // LeafNode::LeafObjectsSizeMax (Node.h:618)
+  ta.ids = d_ids;
+  ta.insert_flag = d_flag;
+  // NGT_AMD_BUILD_REPL_CAP: a smaller table, so that small batches fill it
+  ta.repl_cap = 256;
+  if (const char* v = ngt_amd::knob("NGT_AMD_BUILD_REPL_CAP")) ta.repl_cap = (uint32_t)std::min(256, std::max(0, atoi(v)));
+  ta.n = n;
+  ta.error = ix->error.p;
+  return ta;
+}
+
+// the end of a batch: the tree's node counts and the device error flags
+int finish_batch(ngt_amd_index* ix, BuildState& b, hipStream_t s) {
+  uint32_t hc[3];
+  int herr = 0;
+  HIP_OK(hipMemcpyAsync(hc, b.counts.p, sizeof hc, hipMemcpyDeviceToHost, s));
+  HIP_OK(hipMemcpyAsync(&herr, ix->error.p, sizeof(int), hipMemcpyDeviceToHost, s));
+  HIP_OK(hipStreamSynchronize(s));
+  int serr = 0;  // the insertion searches' flag (their launch context on s)
+  if (take_device_error(ix, s, &serr)) return -1;
+  herr |= serr;
+  if (herr) {
+    (void)hipMemset(ix->error.p, 0, sizeof(int));
+    return fail("ngt_amd_build_insert: device error flag %d (1 unchecked-set spill full; DVP tree: 2 already "
+                "existed, 8 all split distances equal, 16 node capacity, 32 illegal pivot)", herr);
+  }
+  b.n_leaf = hc[0];
+  b.n_internal = hc[1];
+  b.root = hc[2];
+  return 0;
+}
+
+// KNNG: steps a-c of the header for the objects of `todo`, in id order.
+int insert_knng(ngt_amd_index* ix, BuildState& b, const std::vector<uint32_t>& todo) {
+  hipStream_t s = ix->stream;
+  const uint64_t rb = ix->row_bytes;
+  const uint32_t B = (uint32_t)b.batch_size, E = (uint32_t)b.edge_size_for_creation, K1 = E + 1;
+  DevBuf<uint32_t> d_ids, d_ri, d_rn, d_li, d_ln;
+  DevBuf<float> d_rd, d_ld;
+  DevBuf<uint8_t> d_q, d_flag;
+  HIP_OK(d_ids.alloc(B));
+  HIP_OK(d_ri.alloc((size_t)B * K1));
+  HIP_OK(d_rd.alloc((size_t)B * K1));
+  HIP_OK(d_rn.alloc(B));
+  HIP_OK(d_li.alloc((size_t)B * E));
+  HIP_OK(d_ld.alloc((size_t)B * E));
+  HIP_OK(d_ln.alloc(B));
+  HIP_OK(d_flag.alloc(B));
+  std::vector<uint32_t> h_li((size_t)B * E), h_ln(B);
+  std::vector<float> h_ld((size_t)B * E);
+  // NGT_AMD_BUILD_PROFILE=1: per-stage wall time (stream synchronised at each mark)
+  const bool prof = ngt_amd::knob("NGT_AMD_BUILD_PROFILE") != nullptr;
+  double st[3] = {0, 0, 0};
+  auto t_last = std::chrono::steady_clock::now();
+  auto mark = [&](int i) {
+    if (!prof) return;
+    (void)hipStreamSynchronize(s);
+    auto t = std::chrono::steady_clock::now();
+    st[i] += std::chrono::duration<double>(t - t_last).count();
+    t_last = t;
+  };
+  for (size_t pos = 0; pos < todo.size(); pos += B) {
+    const uint32_t n = (uint32_t)std::min<size_t>(B, todo.size() - pos);
+    const uint32_t* ids = todo.data() + pos;
+    if (ensure_tree_capacity(ix, b, 4 * n + 4, n + 1)) return -1;
+    HIP_OK(hipMemcpyAsync(d_ids.p, ids, n * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    // ---- a. the exact E + 1 nearest: the stored rows are the queries ----------
+    const uint8_t* q = ix->rows.p + (uint64_t)ids[0] * rb;
+    if (ids[n - 1] - ids[0] != n - 1) {  // removed rows in between: the batch's rows side by side
+      HIP_OK(d_q.alloc((size_t)n * rb));
+      HIP_OK(launch_gather_rows(d_q.p, ix->rows.p, rb, d_ids.p, n, s));
+      q = d_q.p;
+    }
+    if (ngt_amd_linear_search_device(ix, q, rb, n, K1, (double)FLT_MAX, d_ri.p, d_rd.p, d_rn.p, s)) return -1;
+    mark(0);
+    // ---- b. moveFrom, the lists, the adjacency rows, the tree flags ------------
+    KnngListArgs ka{};
+    ka.res_ids = d_ri.p;
+    ka.res_dists = d_rd.p;
+    ka.res_n = d_rn.p;
+    ka.K1 = K1;
+    ka.ids = d_ids.p;
+    ka.n = n;
+    ka.out_ids = d_li.p;
+    ka.out_dists = d_ld.p;
+    ka.out_n = d_ln.p;
+    ka.flag = d_flag.p;
+    ka.adj = ix->adj.p;
+    ka.adj_stride = b.adj_stride;
+    HIP_OK(launch_knng_lists(ka, s));
+    HIP_OK(hipMemcpyAsync(h_li.data(), d_li.p, (size_t)n * E * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIP_OK(hipMemcpyAsync(h_ld.data(), d_ld.p, (size_t)n * E * sizeof(float), hipMemcpyDeviceToHost, s));
+    HIP_OK(hipMemcpyAsync(h_ln.data(), d_ln.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    // ---- c. DVPTree::insert of the batch, from the root --------------------------
+    HIP_OK(launch_tree_insert(tree_insert_args(ix, b, d_ids.p, d_flag.p, n), ix->metric, ix->otype, s));
+    ix->adj_version++;
+    if (finish_batch(ix, b, s)) return -1;
+    mark(1);
+    // ---- insertKNNGNode (Graph.h:607-609): the graph mirror ----------------------
+    for (uint32_t i = 0; i < n; i++) {
+      const uint32_t id = ids[i];
+      if (h_ln[i] > E) return fail("ngt_amd_build_insert: a KNNG list of %u entries", h_ln[i]);
+      auto& objs = b.graph[id];
+      objs.resize(h_ln[i]);
+      for (uint32_t j = 0; j < h_ln[i]; j++) objs[j] = {h_li[(size_t)i * E + j], h_ld[(size_t)i * E + j]};
+      b.in_graph[id] = 1;
+      b.graph_size = std::max<uint64_t>(b.graph_size, (uint64_t)id + 1);
+    }
+    mark(2);
+  }
+  if (prof)
+    fprintf(stderr, "build_insert KNNG %zu objects: scan %.3f s, lists + tree insert %.3f s, host graph %.3f s\n",
+            todo.size(), st[0], st[1], st[2]);
+  return 0;
+}
+
+// The reverse edge target <- (id, distance) of insertANNGNode / insertONNGNode:
+// the sorted addEdge with the identity check (Graph.h:845-873).
+int add_edge(BuildState& b, uint32_t target, uint32_t id, float distance, std::vector<uint32_t>& dirty) {
+  auto& node = b.graph[target];
+  const std::pair<uint32_t, float> e{id, distance};
+  auto it = std::lower_bound(node.begin(), node.end(), e, od_less);
+  if (it != node.end() && it->first == id) return fail("NGT::addEdge: already existed! %u:%u", it->first, id);
+  if ((uint64_t)(it - node.begin()) < b.adj_stride) dirty.push_back(target);
+  node.insert(it, e);
+  return 0;
+}
+
+// addEdgeDeletingExcessEdges (Graph.h:888-934)
+int add_edge_deleting_excess(BuildState& b, uint32_t target, uint32_t id, float distance,
+                             std::vector<uint32_t>& dirty) {
+  auto& node = b.graph[target];
+  const size_t k_edge = (size_t)b.edge_size_for_creation - 1;
+  if (node.size() > k_edge && node[k_edge].second >= distance) {
+    const std::pair<uint32_t, float> last = node[k_edge];
+    if (last.first >= b.graph.size() || !b.in_graph[last.first])
+      return fail("get: Not in-memory or invalid offset of node. idx=%u size=%zu", last.first, b.graph.size());
+    auto& linked = b.graph[last.first];
+    if (linked.size() > k_edge && last.second >= linked[k_edge].second) {
+      node.erase(node.begin() + k_edge);
+      if (k_edge < b.adj_stride) dirty.push_back(target);
+      const std::pair<uint32_t, float> back{target, last.second};
+      auto it = std::lower_bound(linked.begin(), linked.end(), back, od_less);
+      if (it == linked.end() || it->first != target) {
+        char found[48] = "";
+        if (it != linked.end()) snprintf(found, sizeof found, "%u:", it->first);
+        // the reference prints the edge now at that rank of the shortened list
+        const std::pair<uint32_t, float> now = node.size() > k_edge ? node[k_edge] : std::pair<uint32_t, float>{0u, 0.f};
+        return fail("addEdge: Cannot remove. (b) %u,%u,%u,%g:NGT::removeEdge: Cannot found %s%u", target, id,
+                    now.first, now.second, found, target);
+      }
+      if ((uint64_t)(it - linked.begin()) < b.adj_stride) dirty.push_back(last.first);
+      linked.erase(it);
+    }
+  }
+  return add_edge(b, target, id, distance, dirty);
+}
+
+}  // namespace
+
 extern "C" int ngt_amd_build_insert(ngt_amd_index* ix, uint64_t first_id, uint64_t end_id) {
   if (!ix || !ix->build) return fail("ngt_amd_build_insert: call ngt_amd_build_begin first");
   HIP_OK(hipSetDevice(ix->device));
@@ -147,6 +384,7 @@ extern "C" int ngt_amd_build_insert(ngt_amd_index* ix, uint64_t first_id, uint64
   std::vector<uint32_t> todo;
   for (uint64_t id = first_id; id < end_id; id++)
     if (ix->h_valid[id] && !b.in_graph[id]) todo.push_back((uint32_t)id);
+  if (b.graph_type == NGT_AMD_GRAPH_KNNG) return insert_knng(ix, b, todo);
 
   const uint32_t B = (uint32_t)b.batch_size, K = (uint32_t)b.edge_size_for_creation;
   struct Ev {
@@ -331,35 +569,10 @@ extern "C" int ngt_amd_build_insert(ngt_amd_index* ix, uint64_t first_id, uint64
     mark(2);
 
     // ---- 4. DVPTree::insert of the batch (device, overlaps the host graph work)
-    TreeBuildArgs ta{};
-    ta.rows = ix->rows.p;
-    ta.row_bytes = rb;
-    ta.dp = (int)ix->dp;
-    ta.lf_parent = b.lf_parent.p;
-    ta.lf_has_pivot = b.lf_has_pivot.p;
-    ta.lf_pivot = b.lf_pivot.p;
-    ta.lf_count = b.lf_count.p;
-    ta.lf_ids = b.lf_ids.p;
-    ta.lf_dist = b.lf_dist.p;
-    ta.leaf_cap = kLeafCap;
-    ta.in_parent = b.in_parent.p;
-    ta.in_pivot = b.in_pivot.p;
-    ta.in_child = b.in_child.p;
-    ta.in_border = b.in_border.p;
-    ta.counts = b.counts.p;
-    ta.leaf_cap_nodes = b.leaf_cap_nodes;
-    ta.in_cap_nodes = b.in_cap_nodes;
-    ta.leaf_size = 100;  // LeafNode::LeafObjectsSizeMax (Node.h:618)
-    ta.ids = d_ids.p;
-    ta.insert_flag = d_flag.p;
+    TreeBuildArgs ta = tree_insert_args(ix, b, d_ids.p, d_flag.p, n);
     ta.pre_leaf = d_pleaf.p;
     ta.pre_count = d_pcnt.p;
     ta.pre_dist = d_pdist.p;
-    // NGT_AMD_BUILD_REPL_CAP: a smaller table, so that small batches fill it
-    ta.repl_cap = 256;
-    if (const char* v = ngt_amd::knob("NGT_AMD_BUILD_REPL_CAP")) ta.repl_cap = (uint32_t)std::min(256, std::max(0, atoi(v)));
-    ta.n = n;
-    ta.error = ix->error.p;
     // the merged lists go to the host while the tree insertion runs
     HIP_OK(hipMemcpyAsync(h_mi.data(), d_mi.p, (size_t)n * K * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     HIP_OK(hipMemcpyAsync(h_md.data(), d_md.p, (size_t)n * K * sizeof(float), hipMemcpyDeviceToHost, s));
@@ -369,7 +582,8 @@ extern "C" int ngt_amd_build_insert(ngt_amd_index* ix, uint64_t first_id, uint64
     mark(4);
     HIP_OK(hipEventSynchronize(ev_copy.e));
 
-    // ---- insertANNGNode (Graph.h:611-625): the node, then the reverse edges --
+    // ---- insertANNGNode (Graph.h:611-625): the node, then the reverse edges;
+    //      insertIANNGNode (:628-635) and insertONNGNode (:637-655) likewise ------
     std::vector<uint32_t> dirty;
     for (uint32_t i = 0; i < n; i++) {
       const uint32_t id = ids[i];
@@ -379,13 +593,19 @@ extern "C" int ngt_amd_build_insert(ngt_amd_index* ix, uint64_t first_id, uint64
       b.in_graph[id] = 1;
       b.graph_size = std::max<uint64_t>(b.graph_size, (uint64_t)id + 1);
       dirty.push_back(id);
-      for (const auto& r : objs) {
-        auto& node = b.graph[r.first];
-        const std::pair<uint32_t, float> e{id, r.second};
-        auto it = std::lower_bound(node.begin(), node.end(), e, od_less);
-        if (it != node.end() && it->first == id) return fail("NGT::addEdge: already existed! %u:%u", it->first, id);
-        if ((uint64_t)(it - node.begin()) < b.adj_stride) dirty.push_back(r.first);
-        node.insert(it, e);
+      if (b.graph_type == NGT_AMD_GRAPH_IANNG) {
+        // the job's results, not the stored list: a deletion may shorten that one
+        const std::vector<std::pair<uint32_t, float>> results(objs);
+        for (const auto& r : results)
+          if (add_edge_deleting_excess(b, r.first, id, r.second, dirty)) return -1;
+      } else if (b.graph_type == NGT_AMD_GRAPH_ONNG) {
+        const size_t in = std::min<size_t>(objs.size(), (size_t)b.incoming_edge);
+        for (size_t j = 0; j < in; j++)
+          if (add_edge(b, objs[j].first, id, objs[j].second, dirty)) return -1;
+        if (objs.size() > (size_t)b.outgoing_edge) objs.resize(b.outgoing_edge);
+      } else {
+        for (const auto& r : objs)
+          if (add_edge(b, r.first, id, r.second, dirty)) return -1;
       }
     }
     mark(3);
@@ -403,22 +623,7 @@ extern "C" int ngt_amd_build_insert(ngt_amd_index* ix, uint64_t first_id, uint64
     HIP_OK(d_vals.upload(vals.data(), vals.size()));
     HIP_OK(launch_adj_scatter(ix->adj.p, b.adj_stride, d_dirty.p, d_vals.p, (uint32_t)dirty.size(), s));
     ix->adj_version++;
-    uint32_t hc[3];
-    int herr = 0;
-    HIP_OK(hipMemcpyAsync(hc, b.counts.p, sizeof hc, hipMemcpyDeviceToHost, s));
-    HIP_OK(hipMemcpyAsync(&herr, ix->error.p, sizeof(int), hipMemcpyDeviceToHost, s));
-    HIP_OK(hipStreamSynchronize(s));
-    int serr = 0;  // the insertion searches' flag (their launch context on s)
-    if (take_device_error(ix, s, &serr)) return -1;
-    herr |= serr;
-    if (herr) {
-      (void)hipMemset(ix->error.p, 0, sizeof(int));
-      return fail("ngt_amd_build_insert: device error flag %d (1 unchecked-set spill full; DVP tree: 2 already "
-                  "existed, 8 all split distances equal, 16 node capacity, 32 illegal pivot)", herr);
-    }
-    b.n_leaf = hc[0];
-    b.n_internal = hc[1];
-    b.root = hc[2];
+    if (finish_batch(ix, b, s)) return -1;
     mark(5);
   }
   if (prof)

@@ -9,6 +9,9 @@
 //    definition (each may split the leaf the next one descends to), so one
 //    wave runs the batch: every distance is one quad's comparator, and the
 //    101 x 101 distance matrix of a split uses all 16 quads.
+//  * ngt_knng_lists_kernel : a KNNG batch's lists from its exact E + 1 nearest
+//    (ObjectDistances::moveFrom, lib/NGT/ObjectSpace.h:70-88), one wave per
+//    object, with the adjacency rows and the tree-insertion flags.
 //  * ngt_adj_scatter_kernel : refresh rows of the padded search adjacency
 //    (the first edgeSizeForSearch ids of each changed node).
 #include <hip/hip_runtime.h>
@@ -447,6 +450,45 @@ __global__ void __launch_bounds__(64) ngt_batch_merge_kernel(BatchMergeArgs a) {
   }
 }
 
+// One wave per batch object: ObjectDistances::moveFrom (ObjectSpace.h:70-88)
+// on its E + 1 nearest in (distance, id) order.  The list has one place fewer
+// than the results and is filled from the far end with every entry that is
+// not the object itself: the object leaves, or -- when it is not among the
+// E + 1, more than E duplicates with smaller ids being as near -- the nearest
+// entry does.  The list goes to the session's buffers and, zero filled, to
+// the object's row of the padded adjacency.
+__global__ void __launch_bounds__(64) ngt_knng_lists_kernel(KnngListArgs a) {
+  const int lane = lane_id();
+  const uint32_t E = a.K1 - 1;
+  for (uint32_t i = blockIdx.x; i < a.n; i += gridDim.x) {
+    const uint32_t id = a.ids[i];
+    const uint32_t m = a.res_n[i] < a.K1 ? a.res_n[i] : a.K1;
+    const uint32_t* ri = a.res_ids + (uint64_t)i * a.K1;
+    const float* rd = a.res_dists + (uint64_t)i * a.K1;
+    uint32_t drop = 0;
+    for (uint32_t t0 = 0; t0 < m; t0 += 64) {
+      const uint64_t hit = ballot64(t0 + lane < m && ri[t0 + lane] == id);
+      if (hit) {
+        drop = t0 + __ffsll((long long)hit) - 1;
+        break;
+      }
+    }
+    const uint32_t want = m ? m - 1 : 0;
+    for (uint32_t t = lane; t < want; t += 64) {
+      const uint32_t src = t < drop ? t : t + 1;
+      a.out_ids[(uint64_t)i * E + t] = ri[src];
+      a.out_dists[(uint64_t)i * E + t] = rd[src];
+    }
+    uint32_t* arow = a.adj + (uint64_t)id * a.adj_stride;
+    for (uint32_t t = lane; t < a.adj_stride; t += 64) arow[t] = t < want ? ri[t < drop ? t : t + 1] : 0u;
+    if (lane == 0) {
+      a.out_n[i] = want;
+      // the tree gets the object unless it duplicates its nearest neighbour
+      a.flag[i] = (want == 0 || rd[drop == 0 ? 1 : 0] != 0.0f) ? 1 : 0;
+    }
+  }
+}
+
 // Rows `nodes[i]` of the padded adjacency <- vals[i][0..stride).
 __global__ void __launch_bounds__(256) ngt_adj_scatter_kernel(uint32_t* adj, uint64_t stride,
                                                               const uint32_t* nodes, const uint32_t* vals,
@@ -540,6 +582,13 @@ hipError_t launch_batch_pairs(const BatchPairArgs& a, int metric, int otype, hip
 hipError_t launch_batch_merge(const BatchMergeArgs& a, hipStream_t s) {
   if (a.n == 0) return hipSuccess;
   hipLaunchKernelGGL(ngt_batch_merge_kernel, dim3(a.n < 4096 ? a.n : 4096), dim3(64), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_knng_lists(const KnngListArgs& a, hipStream_t s) {
+  if (a.n == 0) return hipSuccess;
+  if (a.K1 < 2) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(ngt_knng_lists_kernel, dim3(a.n < 4096 ? a.n : 4096), dim3(64), 0, s, a);
   return hipGetLastError();
 }
 

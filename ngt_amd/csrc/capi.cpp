@@ -315,13 +315,20 @@ std::string fetch_session(CapiIndex* ix, bool after_build) {
 }
 
 // GraphAndTreeIndex::createIndex for the objects appended since the last
-// build: ANNG with the tree, on the device; the host mirror receives the
-// graph (CSR + distances) and the DVP tree for ngt_save_index and searches.
-std::string build_anng(CapiIndex* ix) {
+// build: an ANNG, KNNG, IANNG or ONNG with the tree, on the device; the host
+// mirror receives the graph (CSR + distances) and the DVP tree for
+// ngt_save_index and searches.
+std::string build_graph(CapiIndex* ix) {
   std::unique_lock<std::shared_mutex> wl(ix->rw);
   HostIndex& h = ix->host;
   if (h.prop.edge_size_for_creation == 0) return "";  // createIndex returns at once (Index.cpp:1162-1164)
-  if (h.prop.graph_type != 1) return "index construction supports graphType ANNG only";
+  const int gt = h.prop.graph_type;
+  // BKNNG re-inserts every node on each createIndex from an empty graph's random
+  // seeds; DNNG has no insertion rule in the reference (Graph.h:558-560)
+  if (gt != NGT_AMD_GRAPH_ANNG && gt != NGT_AMD_GRAPH_KNNG && gt != NGT_AMD_GRAPH_ONNG && gt != NGT_AMD_GRAPH_IANNG)
+    return "index construction supports graphType ANNG, KNNG, IANNG and ONNG only";
+  if (gt == NGT_AMD_GRAPH_ONNG && h.prop.truncation_threshold != 0)
+    return "NGT::insertONNGNode: truncation should be disabled!";  // Graph.h:638-642
   if (h.prop.index_type != 0) return "index construction supports GraphAndTree indexes only";
   bool has_graph = false;
   for (uint64_t v = 0; v < h.nrows && v + 1 < h.edge_off.size() && !has_graph; v++)
@@ -336,7 +343,13 @@ std::string build_anng(CapiIndex* ix) {
   p.batch_size_for_creation = h.prop.batch_size_for_creation;
   p.seed_size = h.prop.seed_size;
   p.epsilon_for_creation = (float)h.prop.epsilon_for_creation;
+  p.graph_type = gt;
   if (ngt_amd_build_begin(ix->dev, &p)) return amd_err();
+  // from here on the device copy serves the session, whatever the outcome
+  ix->device_stale = true;
+  if (gt == NGT_AMD_GRAPH_ONNG &&
+      ngt_amd_build_set_onng_edges(ix->dev, h.prop.outgoing_edge, h.prop.incoming_edge))
+    return amd_err();
   if (has_graph) {
     // incremental: the objects without a node join the existing graph and tree
     const ngt_amd::HostTree& t = h.tree;
@@ -910,7 +923,7 @@ bool ngt_create_index(NGTIndex index, uint32_t pool_size, NGTError error) {
   }
   CapiIndex* ix = static_cast<CapiIndex*>(index);
   HostIndex& h = ix->host;
-  std::string e = build_anng(ix);
+  std::string e = build_graph(ix);
   if (!e.empty()) {
     set_error(error, __FUNCTION__, e);
     return false;

@@ -240,6 +240,8 @@ struct RemoveScratch {
 struct BuildState {
   int32_t edge_size_for_creation = 10, edge_size_for_search = 40, batch_size = 200, seed_size = 10;
   float epsilon_for_creation = 0.1f;
+  int32_t graph_type = NGT_AMD_GRAPH_ANNG;         // the insertion rule (build.cpp)
+  int32_t outgoing_edge = 10, incoming_edge = 80;  // ONNG at insertion (Graph.h:637-655)
   std::vector<std::vector<std::pair<uint32_t, float>>> graph;  // graph repository, slot = object id
   std::vector<uint8_t> in_graph;
   uint64_t graph_size = 0;       // GraphRepository::size() (max inserted id + 1, 0 when empty)

@@ -95,6 +95,9 @@ void HostProperty::set_defaults() {
   epsilon_for_creation = 0.1;
   batch_size_for_creation = 200;
   prefetch_offset = prefetch_size = 0;
+  outgoing_edge = 10;            // Graph.h:399
+  incoming_edge = 80;            // Graph.h:400
+  truncation_threshold = 0;
 }
 
 void HostProperty::from_kv() {
@@ -116,6 +119,9 @@ void HostProperty::from_kv() {
   epsilon_for_creation = getf(kv, "EpsilonForCreation", epsilon_for_creation);
   prefetch_offset = (int32_t)getl(kv, "PrefetchOffset", 0);
   prefetch_size = (int32_t)getl(kv, "PrefetchSize", 0);
+  outgoing_edge = (int32_t)getl(kv, "OutgoingEdge", outgoing_edge);
+  incoming_edge = (int32_t)getl(kv, "IncomingEdge", incoming_edge);
+  truncation_threshold = (int32_t)getl(kv, "IncrimentalEdgeSizeLimitForTruncation", truncation_threshold);
   it = kv.find("SeedType");
   if (it != kv.end())
     for (int i = 0; i < 5; i++)
@@ -142,6 +148,9 @@ void HostProperty::to_kv() {
   kv["SeedType"] = kSeedTypes[seed_type >= 0 && seed_type < 5 ? seed_type : 0];
   kv["GraphType"] = kGraphTypes[graph_type >= 0 && graph_type < 7 ? graph_type : 1];
   kv["BatchSizeForCreation"] = std::to_string(batch_size_for_creation);
+  kv["OutgoingEdge"] = std::to_string(outgoing_edge);
+  kv["IncomingEdge"] = std::to_string(incoming_edge);
+  kv["IncrimentalEdgeSizeLimitForTruncation"] = std::to_string(truncation_threshold);
   {
     std::ostringstream os;
     os << epsilon_for_creation;
@@ -157,9 +166,6 @@ void HostProperty::to_kv() {
   static const char* kMore[][2] = {{"AccuracyTable", ""},
                                    {"BuildTimeLimit", "0"},
                                    {"EdgeSizeLimitForCreation", "5"},
-                                   {"IncomingEdge", "80"},
-                                   {"IncrimentalEdgeSizeLimitForTruncation", "0"},
-                                   {"OutgoingEdge", "10"},
                                    {"PathAdjustmentInterval", "0"},
                                    {"ThreadPoolSize", "32"},
                                    {"TruncationThreadPoolSize", "8"}};

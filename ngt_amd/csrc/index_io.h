@@ -34,6 +34,9 @@ struct HostProperty {
   double epsilon_for_creation = 0.1;
   int32_t batch_size_for_creation = 200;
   int32_t prefetch_offset = 0, prefetch_size = 0;
+  int32_t outgoing_edge = 10;     // ONNG at insertion (Graph.h:399-400, 637-655)
+  int32_t incoming_edge = 80;
+  int32_t truncation_threshold = 0;  // IncrimentalEdgeSizeLimitForTruncation
   void set_defaults();            // NGT::Property defaults (Index.h:45-104, Graph.h:386-402)
   // the object space's dimension: SparseJaccard keeps one more slot for the
   // 0 terminator (GraphIndex::constructObjectSpace, Index.cpp:484-490)

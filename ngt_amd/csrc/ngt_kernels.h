@@ -311,8 +311,27 @@ struct BatchMergeArgs {
   uint8_t* flag;                 // [n] DVP-tree insertion flag (Index.cpp:1201-1203)
 };
 
+// KNNG: ObjectDistances::moveFrom (ObjectSpace.h:70-88) on the batch's exact
+// E + 1 nearest, sorted by (distance, id): the object itself leaves the list,
+// or, when more than E nearer-or-equal objects kept it out, the nearest entry.
+struct KnngListArgs {
+  const uint32_t* res_ids;       // [n][K1] linear-search results, K1 = edgeSizeForCreation + 1
+  const float* res_dists;
+  const uint32_t* res_n;         // [n]
+  uint32_t K1;
+  const uint32_t* ids;           // [n] batch ids
+  uint32_t n;
+  uint32_t* out_ids;             // [n][K1 - 1]
+  float* out_dists;
+  uint32_t* out_n;               // [n]
+  uint8_t* flag;                 // [n] DVP-tree insertion flag (Index.cpp:1201-1203)
+  uint32_t* adj;                 // padded search adjacency: row ids[i] <- the list, zero filled
+  uint64_t adj_stride;
+};
+
 hipError_t launch_batch_pairs(const BatchPairArgs& a, int metric, int otype, hipStream_t s);
 hipError_t launch_batch_merge(const BatchMergeArgs& a, hipStream_t s);
+hipError_t launch_knng_lists(const KnngListArgs& a, hipStream_t s);
 hipError_t launch_tree_insert(const TreeBuildArgs& a, int metric, int otype, hipStream_t s);
 hipError_t launch_adj_scatter(uint32_t* adj, uint64_t stride, const uint32_t* nodes, const uint32_t* vals,
                               uint32_t n, hipStream_t s);

@@ -21,6 +21,8 @@ DISTANCE = {
 }
 SEED_TREE, SEED_GIVEN, SEED_RANDOM = 0, 1, 2
 COUNTERS = 8
+# NeighborhoodGraph::GraphType of the types the device constructs (NGT_AMD_GRAPH_*)
+GRAPH_ANNG, GRAPH_KNNG, GRAPH_ONNG, GRAPH_IANNG = 1, 2, 4, 5
 
 
 def padded_dim(dim):
@@ -260,16 +262,21 @@ class DeviceIndex(object):
                                       len(oid), out.ctypes.data))
         return out
 
-    # ---- ANNG construction (GraphAndTreeIndex::createIndex) -----------------
+    # ---- graph construction (GraphAndTreeIndex::createIndex) ----------------
     def build_anng(self, first_id=1, end_id=None, edge_size_for_creation=10, edge_size_for_search=40,
-                   batch_size_for_creation=200, seed_size=10, epsilon_for_creation=0.1, begin=True):
-        """Build the ANNG + DVP tree of the objects on the device; returns
-        (offsets, ids, dists) of the graph and the tree dict (read_tre layout)."""
+                   batch_size_for_creation=200, seed_size=10, epsilon_for_creation=0.1, begin=True,
+                   graph_type=GRAPH_ANNG, outgoing_edge=10, incoming_edge=80):
+        """Build the graph + DVP tree of the objects on the device; returns
+        (offsets, ids, dists) of the graph and the tree dict (read_tre layout).
+        graph_type: GRAPH_ANNG (default), GRAPH_KNNG, GRAPH_IANNG or GRAPH_ONNG;
+        outgoing_edge / incoming_edge are the ONNG's two counts."""
         from ._sigs import BuildParams
         if begin:
             prm = BuildParams(edge_size_for_creation, edge_size_for_search, batch_size_for_creation, seed_size,
-                              epsilon_for_creation, 0)
+                              epsilon_for_creation, graph_type)
             _chk(self.L.ngt_amd_build_begin(self.h, byref(prm)))
+            if graph_type == GRAPH_ONNG:
+                _chk(self.L.ngt_amd_build_set_onng_edges(self.h, outgoing_edge, incoming_edge))
         _chk(self.L.ngt_amd_build_insert(self.h, first_id, self.nrows if end_id is None else end_id))
         return self.build_graph(), self.build_tree()
 
