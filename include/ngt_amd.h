@@ -169,13 +169,19 @@ int ngt_amd_last_search_lookahead(const ngt_amd_index *index);
  * params->seed_mode NGT_AMD_SEED_RANDOM or NGT_AMD_SEED_TREE, k <= 64.
  * Results, distances and counters equal ngt_amd_search's.  Thread-safe.
  * Returns 0 when served, 1 when this index or request is not one the grid
- * serves (call ngt_amd_search instead), -1 on error. */
+ * serves (call ngt_amd_search instead), -1 on error.  A tree with a leaf
+ * that holds no ids (removals emptied it) is not served: see below. */
 int ngt_amd_search_served(ngt_amd_index *index, const ngt_amd_search_params *params, const float *query,
                           uint32_t *ids, float *dists, uint32_t *n, uint64_t *counters);
 /* Stop the serving grid now (it also stops by itself after a short idle time). */
 int ngt_amd_serve_stop(ngt_amd_index *index);
 /* Queries the serving grid answered and grids launched since the index was created. */
 int ngt_amd_serve_stats(ngt_amd_index *index, uint64_t *served, uint64_t *launches);
+/* With NGT_AMD_SEED_TREE on a tree that has a leaf without ids, a query whose
+ * descent ends there takes getRandomSeeds seeds (Index.h:1145-1155) from the
+ * library's rand() stream (ngt_amd_srand), in query order; to find those
+ * queries the call copies the seed counts back and waits on `stream` once
+ * before it enqueues the search.  Any other call only enqueues. */
 int ngt_amd_search_device(ngt_amd_index *index, const ngt_amd_search_params *params,
                           const void *d_queries, uint64_t query_bytes, uint32_t nq,
                           const uint32_t *d_seeds, const uint64_t *d_seed_off, uint32_t *d_ids,

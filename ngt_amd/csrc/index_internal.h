@@ -304,6 +304,7 @@ struct ngt_amd_index {
   std::vector<uint8_t> h_graph_empty;
   // tree
   bool has_tree = false;
+  bool tree_has_empty_leaf = false;  // some leaf slot past 0 holds no ids (ngt_amd_index_set_tree)
   DevBuf<uint8_t> in_pivot;
   DevBuf<uint32_t> in_child, leaf_ids;
   DevBuf<float> in_border;

@@ -231,6 +231,9 @@ extern "C" int ngt_amd_index_set_tree(ngt_amd_index* ix, const void* in_pivot, u
   ix->children = children;
   ix->root = root;
   ix->has_tree = true;
+  // a leaf slot without ids (slot 0 is never used): a descent may end there
+  ix->tree_has_empty_leaf = false;
+  for (uint32_t l = 1; l < n_leaf; l++) ix->tree_has_empty_leaf |= leaf_off[l + 1] == leaf_off[l];
   ix->tree_version++;
   return 0;
 }
@@ -623,6 +626,8 @@ static int launch_planned(ngt_amd_index* ix, SearchCtx* c, const SearchPlan& pla
   return 0;
 }
 
+static int fill_empty_tree_seeds(ngt_amd_index* ix, SearchCtx* c, uint32_t nq, hipStream_t s);
+
 // One graph search: plan it (search_plan.cpp decides the kernel and every LDS
 // capacity), then gather what the plan needs and launch.
 static int run_search(ngt_amd_index* ix, SearchCtx* c, const ngt_amd_search_params* prm, const void* d_queries,
@@ -669,6 +674,7 @@ static int run_search(ngt_amd_index* ix, SearchCtx* c, const ngt_amd_search_para
 
   if (prm->seed_mode == NGT_AMD_SEED_TREE) {
     if (run_tree_seeds(ix, c, d_queries, query_bytes, nq, prm->k, prm->all_leaf_nodes, s)) return -1;
+    if (ix->tree_has_empty_leaf && !ix->h_graph_empty.empty() && fill_empty_tree_seeds(ix, c, nq, s)) return -1;
     a.seeds = c->seeds.p;
     a.seed_stride = kTreeSeedStride;
     a.seed_count = c->seed_count.p;
@@ -714,31 +720,72 @@ extern "C" void ngt_amd_srand(unsigned int seed) {
   seed_rand().seed(seed);
 }
 
+// One GraphIndex::getRandomSeeds (Index.h:775-801) appended to `seeds`; the
+// caller holds g_rand_mu.
+static void draw_random_seeds(ngt_amd_index* ix, GlibcRandHost& rnd, std::vector<uint32_t>& seeds) {
+  const size_t start = seeds.size();
+  const size_t repo = ix->nrows == 0 ? 0 : ix->nrows - 1;
+  const size_t ss = std::min<size_t>(repo, (size_t)std::max(ix->seed_size, 0));
+  size_t empty = 0;
+  while (seeds.size() - start < ss) {
+    double random = ((double)rnd.next() + 1.0) / ((double)RAND_MAX + 2.0);
+    size_t idx = (size_t)floor((double)repo * random) + 1;
+    if (ix->h_graph_empty[idx]) {
+      if (++empty > repo) break;
+      continue;
+    }
+    if (std::find(seeds.begin() + start, seeds.end(), (uint32_t)idx) != seeds.end()) continue;
+    seeds.push_back((uint32_t)idx);
+  }
+}
+
 std::vector<uint32_t> ngt_amd::random_seed_lists(ngt_amd_index* ix, uint32_t nq, std::vector<uint64_t>& off) {
-  // GraphIndex::getRandomSeeds (Index.h:775-801) over the rand() stream, one
-  // query after another as the reference's callers do.
+  // one query after another over the rand() stream, as the reference's callers do
   std::lock_guard<std::mutex> lk(g_rand_mu);
   GlibcRandHost& rnd = seed_rand();
   std::vector<uint32_t> seeds;
   off.assign(nq + 1, 0);
-  size_t repo = ix->nrows == 0 ? 0 : ix->nrows - 1;
-  size_t ss = std::min<size_t>(repo, (size_t)std::max(ix->seed_size, 0));
   for (uint32_t q = 0; q < nq; q++) {
-    size_t start = seeds.size();
-    size_t empty = 0;
-    while (seeds.size() - start < ss) {
-      double random = ((double)rnd.next() + 1.0) / ((double)RAND_MAX + 2.0);
-      size_t idx = (size_t)floor((double)repo * random) + 1;
-      if (ix->h_graph_empty[idx]) {
-        if (++empty > repo) break;
-        continue;
-      }
-      if (std::find(seeds.begin() + start, seeds.end(), (uint32_t)idx) != seeds.end()) continue;
-      seeds.push_back((uint32_t)idx);
-    }
+    draw_random_seeds(ix, rnd, seeds);
     off[q + 1] = seeds.size();
   }
   return seeds;
+}
+
+// GraphIndex::search (Index.h:1145-1155): a query whose leaf holds no object --
+// removals emptied it -- has no tree seeds and takes getSeedsFromGraph's
+// random ones, in query order.  Only a tree with an empty leaf pays the copy
+// of the counts and the wait.
+static int fill_empty_tree_seeds(ngt_amd_index* ix, SearchCtx* c, uint32_t nq, hipStream_t s) {
+  std::vector<uint32_t> cnt(nq);
+  HIP_OK(hipMemcpyAsync(cnt.data(), c->seed_count.p, (size_t)nq * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  HIP_OK(hipStreamSynchronize(s));
+  std::vector<uint32_t> seeds;
+  std::vector<std::pair<uint32_t, uint32_t>> at;  // (query, first seed)
+  {
+    std::lock_guard<std::mutex> lk(g_rand_mu);
+    GlibcRandHost& rnd = seed_rand();
+    for (uint32_t q = 0; q < nq; q++) {
+      if (cnt[q]) continue;
+      at.emplace_back(q, (uint32_t)seeds.size());
+      draw_random_seeds(ix, rnd, seeds);
+    }
+  }
+  if (at.empty()) return 0;
+  // the seed rows of those queries and the patched counts, then one wait: the
+  // host vectors must outlive the copies
+  for (size_t i = 0; i < at.size(); i++) {
+    const uint32_t q = at[i].first, b = at[i].second;
+    const uint32_t e = i + 1 < at.size() ? at[i + 1].second : (uint32_t)seeds.size();
+    const uint32_t n = std::min<uint32_t>(e - b, kTreeSeedStride);
+    cnt[q] = n;
+    if (n)
+      HIP_OK(hipMemcpyAsync(c->seeds.p + (size_t)q * kTreeSeedStride, seeds.data() + b, (size_t)n * sizeof(uint32_t),
+                            hipMemcpyHostToDevice, s));
+  }
+  HIP_OK(hipMemcpyAsync(c->seed_count.p, cnt.data(), (size_t)nq * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+  HIP_OK(hipStreamSynchronize(s));
+  return 0;
 }
 
 extern "C" int ngt_amd_search_device(ngt_amd_index* ix, const ngt_amd_search_params* prm,

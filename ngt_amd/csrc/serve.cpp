@@ -226,6 +226,9 @@ int serve_args(ngt_amd_index* ix, const ngt_amd_search_params* prm, SearchArgs& 
   const bool tree = prm->seed_mode == NGT_AMD_SEED_TREE;
   if (!tree && prm->seed_mode != NGT_AMD_SEED_RANDOM) return 1;
   if (tree && !ix->has_tree) return 1;
+  // a descent may end in a leaf without ids: the launch path gives such a query
+  // getRandomSeeds seeds (fill_empty_tree_seeds), the grid's in-kernel descent cannot
+  if (tree && ix->tree_has_empty_leaf) return 1;
   if (!tree && ix->seed_size > (int32_t)kServeMaxSeeds) return 1;
   const uint64_t es = ngt_amd_resolve_edge_size(ix, prm->edge_size, prm->epsilon);
   if (es == 0) return 1;

@@ -1,4 +1,4 @@
-"""Readers for NGT 1.13.8 index files (test infrastructure).
+"""Readers, and a writer of obj, for NGT 1.13.8 index files (test infrastructure).
 
 These parse the reference's on-disk formats into numpy arrays so that the
 golden-vector generator and the tests can inspect reference-built indexes:
@@ -62,9 +62,31 @@ def read_obj(path, dim, dtype):
     return rows, valid
 
 
+def obj_bytes(rows, dim, valid=None):
+    """Inverse of read_obj: rows[n, >= dim] (row 0 the dummy slot) of float32 or
+    uint8 -> the bytes of the obj file.  valid[i] == 0 (and slot 0 always) is a
+    removed slot, written as '-'; the padding columns are not stored."""
+    rows = np.asarray(rows)
+    if rows.dtype not in (np.dtype(np.float32), np.dtype(np.uint8)):
+        raise ValueError("obj rows are float32 or uint8, not %s" % rows.dtype)
+    n = len(rows)
+    out = [struct.pack("<Q", n)]
+    for i in range(n):
+        if i == 0 or (valid is not None and not valid[i]):
+            out.append(b"-")
+        else:
+            out.append(b"+" + np.ascontiguousarray(rows[i, :dim]).tobytes())
+    return b"".join(out)
+
+
+def write_obj(path, rows, dim, valid=None):
+    with open(path, "wb") as f:
+        f.write(obj_bytes(rows, dim, valid))
+
+
 def read_grp(path):
-    """Returns (offsets[n+1] uint64, ids uint32, dists float32)."""
-    raw = open(path, "rb").read()
+    """Returns (offsets[n+1] uint64, ids uint32, dists float32); `path` may be the file's bytes."""
+    raw = path if isinstance(path, bytes) else open(path, "rb").read()
     n = struct.unpack_from("<Q", raw, 0)[0]
     off = 8
     offsets = np.zeros(n + 1, dtype=np.uint64)
@@ -98,7 +120,7 @@ def read_tre(path, dim, dtype):
             [n_in, 5] (raw Node::ID), in_border [n_in, 4], in_valid; root raw id.
     """
     dtype = np.dtype(dtype)
-    raw = open(path, "rb").read()
+    raw = path if isinstance(path, bytes) else open(path, "rb").read()
     dp = padded_dim(dim)
     nbytes = dim * dtype.itemsize
     off = 0

@@ -35,17 +35,21 @@ def outgoing(node, nid, results):
 
 def add_edge(node, nid, dist):
     """GraphIndex::addEdge(node, id, distance, identityCheck=false): lower_bound
-    of (distance, id); nothing if that position holds the same id, else insert."""
+    of (distance, id); nothing if that position holds the same id, else insert.
+    -> whether the edge went in."""
     keys = [_key(e) for e in node]
     p = bisect.bisect_left(keys, (dist, nid))
     if p < len(node) and node[p][0] == nid:
-        return
+        return False
     node.insert(p, (nid, dist))
+    return True
 
 
-def merge(graph, first, results, incoming):
+def merge(graph, first, results, incoming, stats=None):
     """Steps 2 and 3 of one batch, in place.  results[q]: the result list of
-    node first + q in result order; queries past the last row are ignored."""
+    node first + q in result order; queries past the last row are ignored.
+    `stats`, when a dict, counts under "incoming_at_a_present_distance" the
+    incoming edges that went into a list already holding their distance."""
     n = len(graph)
     results = results[:max(0, n - first)]
     for q, res in enumerate(results):
@@ -55,7 +59,9 @@ def merge(graph, first, results, incoming):
     for q, res in enumerate(results):
         for rid, dist in res:
             if rid != first + q:
-                add_edge(graph[rid], first + q, dist)
+                tie = stats is not None and any(e[1] == dist for e in graph[rid])
+                if add_edge(graph[rid], first + q, dist) and tie:
+                    stats["incoming_at_a_present_distance"] = stats.get("incoming_at_a_present_distance", 0) + 1
     return graph
 
 
@@ -94,8 +100,13 @@ def edge_size(prop, explore, epsilon):
     raise ValueError("NGT::getEdgeSize: Invalid edge size parameters %d:%s" % (es, prop["EdgeSizeForSearch"]))
 
 
-def refine(rows, tree, prop, offsets, ids, dists, epsilon, num_edges=0, explore=None, batch_size=10000, threads=8):
-    """The whole refinement of an L2 float index; returns the new CSR."""
+def refine(rows, tree, prop, offsets, ids, dists, epsilon, num_edges=0, explore=None, batch_size=10000, threads=8,
+           metric="l2", valid=None, stats=None):
+    """The whole refinement of an index under `metric`; returns the new CSR.
+    `rows` are the stored rows (float32 or uint8, normalised already where the
+    metric normalises): refineANNG searches with the stored objects themselves.
+    valid[v] == 0 is a removed row: ObjectRepository::isEmpty skips its search
+    and its outgoing step, and it has no results to hand out."""
     import oracle_py as O
     graph = from_csr(offsets, ids, dists)
     n = len(graph)
@@ -104,14 +115,17 @@ def refine(rows, tree, prop, offsets, ids, dists, epsilon, num_edges=0, explore=
     es = edge_size(prop, explore, epsilon)
     seed_size = int(prop["SeedSize"])
     for bid in range(1, n, batch_size):
-        batch = list(range(bid, min(bid + batch_size, n)))
-        off, eid, _ = to_csr(graph)
-        seeds = [O.tree_seeds("l2", tree, rows[v], size, seed_size)[0] for v in batch]
-        ri, rd, rn, _ = O.search_batch("l2", rows, off, eid, rows[batch], seeds, size, np.float32(epsilon),
-                                       edge_size=es, threads=threads)
-        rd = rd.astype(np.float64)
-        results = [[(int(ri[q, j]), float(rd[q, j])) for j in range(int(rn[q]))] for q in range(len(batch))]
-        merge(graph, bid, results, num_edges == 0)
+        batch = [v for v in range(bid, min(bid + batch_size, n)) if valid is None or valid[v]]
+        results = [[] for _ in range(min(bid + batch_size, n) - bid)]
+        if batch:
+            off, eid, _ = to_csr(graph)
+            seeds = [O.tree_seeds(metric, tree, rows[v], size, seed_size, rows.dtype)[0] for v in batch]
+            ri, rd, rn, _ = O.search_batch(metric, rows, off, eid, rows[batch], seeds, size, np.float32(epsilon),
+                                           edge_size=es, threads=threads)
+            rd = rd.astype(np.float64)
+            for q, v in enumerate(batch):
+                results[v - bid] = [(int(ri[q, j]), float(rd[q, j])) for j in range(int(rn[q]))]
+        merge(graph, bid, results, num_edges == 0, stats)
     if num_edges > 0:
         prune(graph, num_edges)
     return to_csr(graph)
