@@ -21,6 +21,9 @@
 // The graph being built is host-side (sorted edge lists, the reference's
 // GraphRepository); the insertion searches read a padded HBM copy of each
 // node's first edgeSizeForSearch edges, refreshed for the nodes a batch touched.
+// Every rule on those lists -- the insertion rules, the sorted addEdge,
+// getRandomSeeds, the host half of removal, the adjacency rows -- is stated in
+// session_graph.h, pure host code; this file is the device work around them.
 //
 // IANNG and ONNG keep steps 1, 2 and 4 and the merge of step 3; only the
 // insertion rule differs (NeighborhoodGraph::insertNode, Graph.h:533-562):
@@ -60,10 +63,8 @@
 // the graph mirror.
 #include <hip/hip_runtime.h>
 #include <float.h>
-#include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
-#include <string.h>
 
 #include <algorithm>
 #include <chrono>
@@ -74,6 +75,7 @@
 #include "index_io.h"
 #include "ngt_kernels.h"
 #include "remove_kernels.h"
+#include "session_graph.h"
 
 using namespace ngt_amd;
 
@@ -119,11 +121,22 @@ int ensure_tree_capacity(ngt_amd_index* ix, BuildState& b, uint32_t extra_leaves
   return 0;
 }
 
-bool od_less(const std::pair<uint32_t, float>& a, const std::pair<uint32_t, float>& b) {
-  // ObjectDistance::operator< (Common.h:1946-1952): distance, then id
-  if (a.second != b.second) return a.second < b.second;
-  return a.first < b.first;
-}
+// NGT_AMD_BUILD_PROFILE=1: wall time per stage, summed over a call.  With a
+// stream, every mark synchronises it first.
+struct StageClock {
+  bool on = ngt_amd::knob("NGT_AMD_BUILD_PROFILE") != nullptr;
+  hipStream_t sync = nullptr;
+  double st[6] = {0, 0, 0, 0, 0, 0};
+  std::chrono::steady_clock::time_point t_last = std::chrono::steady_clock::now();
+  void start() { t_last = std::chrono::steady_clock::now(); }
+  void mark(int i) {
+    if (!on) return;
+    if (sync) (void)hipStreamSynchronize(sync);
+    auto t = std::chrono::steady_clock::now();
+    st[i] += std::chrono::duration<double>(t - t_last).count();
+    t_last = t;
+  }
+};
 
 }  // namespace
 
@@ -137,18 +150,18 @@ extern "C" int ngt_amd_build_begin(ngt_amd_index* ix, const ngt_amd_build_params
   delete ix->build;
   auto* b = new BuildState();
   ix->build = b;
-  b->edge_size_for_creation = prm->edge_size_for_creation;
+  SessionGraph& g = b->g;
+  g.edge_size_for_creation = prm->edge_size_for_creation;
   b->edge_size_for_search = prm->edge_size_for_search;
   b->batch_size = prm->batch_size_for_creation;
   b->seed_size = prm->seed_size;
   b->epsilon_for_creation = prm->epsilon_for_creation;
-  b->graph_type = prm->graph_type == 0 ? NGT_AMD_GRAPH_ANNG : prm->graph_type;
-  if (b->graph_type != NGT_AMD_GRAPH_ANNG && b->graph_type != NGT_AMD_GRAPH_KNNG &&
-      b->graph_type != NGT_AMD_GRAPH_ONNG && b->graph_type != NGT_AMD_GRAPH_IANNG)
+  g.graph_type = prm->graph_type == 0 ? NGT_AMD_GRAPH_ANNG : prm->graph_type;
+  if (g.graph_type != NGT_AMD_GRAPH_ANNG && g.graph_type != NGT_AMD_GRAPH_KNNG &&
+      g.graph_type != NGT_AMD_GRAPH_ONNG && g.graph_type != NGT_AMD_GRAPH_IANNG)
     return fail("ngt_amd_build_begin: graph type %d unsupported (ANNG 1, KNNG 2, ONNG 4 and IANNG 5 are built)",
                 prm->graph_type);
-  b->graph.assign(ix->nrows, {});
-  b->in_graph.assign(ix->nrows, 0);
+  g.reset(ix->nrows);
   b->rnd.seed(1);
   if (ensure_tree_capacity(ix, *b, 64, 16)) return -1;
   // the empty root leaf (DVPTree(), Tree.h:71-78): leaf 1, no parent, no objects
@@ -160,14 +173,14 @@ extern "C" int ngt_amd_build_begin(ngt_amd_index* ix, const ngt_amd_build_params
   // padded search adjacency: each node's first edgeSizeForSearch edges
   const int64_t es = prm->edge_size_for_search;
   if (es < 0 || es > 256) return fail("ngt_amd_build_begin: edge_size_for_search %lld unsupported", (long long)es);
-  b->adj_stride = es == 0 ? 256 : (uint64_t)((es + 15) / 16 * 16);
-  HIP_OK(ix->adj.alloc((size_t)ix->nrows * b->adj_stride));
-  HIP_OK(hipMemset(ix->adj.p, 0, (size_t)ix->nrows * b->adj_stride * sizeof(uint32_t)));
-  ix->adj_stride = b->adj_stride;
+  g.adj_stride = es == 0 ? 256 : (uint64_t)((es + 15) / 16 * 16);
+  HIP_OK(ix->adj.alloc((size_t)ix->nrows * g.adj_stride));
+  HIP_OK(hipMemset(ix->adj.p, 0, (size_t)ix->nrows * g.adj_stride * sizeof(uint32_t)));
+  ix->adj_stride = g.adj_stride;
   ix->adj_version++;
   // the construction's searches read at most adj_stride edges of a list: the
   // padded copy is always the one to use (run_search never rebuilds it here)
-  ix->max_degree = b->adj_stride;
+  ix->max_degree = g.adj_stride;
   ix->has_graph = true;
   ix->edge_size_for_search = prm->edge_size_for_search;
   ix->seed_size = prm->seed_size;
@@ -180,8 +193,8 @@ extern "C" int ngt_amd_build_set_onng_edges(ngt_amd_index* ix, int32_t outgoing_
   if (outgoing_edge < 1 || incoming_edge < 0)
     return fail("ngt_amd_build_set_onng_edges: outgoing_edge %d must be >= 1 and incoming_edge %d >= 0",
                 outgoing_edge, incoming_edge);
-  ix->build->outgoing_edge = outgoing_edge;
-  ix->build->incoming_edge = incoming_edge;
+  ix->build->g.outgoing_edge = outgoing_edge;
+  ix->build->g.incoming_edge = incoming_edge;
   return 0;
 }
 
@@ -241,130 +254,300 @@ int finish_batch(ngt_amd_index* ix, BuildState& b, hipStream_t s) {
   return 0;
 }
 
-// KNNG: steps a-c of the header for the objects of `todo`, in id order.
-int insert_knng(ngt_amd_index* ix, BuildState& b, const std::vector<uint32_t>& todo) {
-  hipStream_t s = ix->stream;
-  const uint64_t rb = ix->row_bytes;
-  const uint32_t B = (uint32_t)b.batch_size, E = (uint32_t)b.edge_size_for_creation, K1 = E + 1;
-  DevBuf<uint32_t> d_ids, d_ri, d_rn, d_li, d_ln;
-  DevBuf<float> d_rd, d_ld;
+// a search from given seeds over the property's edge size (sc.edgeSize default
+// -> edgeSizeForSearch), visited ids hashed in LDS
+ngt_amd_search_params seeded_search_params(uint32_t k, float epsilon, float radius) {
+  ngt_amd_search_params p{};
+  p.k = k;
+  p.epsilon = epsilon;
+  p.radius = radius;
+  p.edge_size = -1;
+  p.seed_mode = NGT_AMD_SEED_GIVEN;
+  p.visited_hash_log2 = 0;
+  return p;
+}
+
+int alloc_descent(DescentBufs& d, uint32_t nq) {
+  HIP_OK(d.tseeds.alloc((size_t)nq * kTreeSeedStride));
+  HIP_OK(d.tcnt.alloc(nq));
+  HIP_OK(d.pleaf.alloc(nq));
+  HIP_OK(d.pcnt.alloc(nq));
+  HIP_OK(d.pdist.alloc(nq));
+  return 0;
+}
+
+// A descent of nq prepared rows over the session's tree that writes each
+// row's leaf, its object count and pivot distance next to the seeds; the
+// caller sets seed_size, k and all_leaf_nodes.
+TreeSeedArgs tree_descent_args(const ngt_amd_index* ix, const BuildState& b, const uint8_t* queries, uint32_t nq,
+                               const DescentBufs& d) {
+  TreeSeedArgs t{};
+  t.queries = queries;
+  t.query_bytes = ix->row_bytes;
+  t.nq = nq;
+  t.dp = (int)ix->dp;
+  t.row_bytes = ix->row_bytes;
+  t.in_pivot = b.in_pivot.p;
+  t.in_child = b.in_child.p;
+  t.in_border = b.in_border.p;
+  t.children = 5;
+  t.root = b.root;
+  t.leaf_count = b.lf_count.p;
+  t.leaf_stride = kLeafCap;
+  t.leaf_ids = b.lf_ids.p;
+  t.seeds = d.tseeds.p;
+  t.seed_stride = kTreeSeedStride;
+  t.seed_count = d.tcnt.p;
+  t.out_leaf = d.pleaf.p;
+  t.out_count = d.pcnt.p;
+  t.out_pdist = d.pdist.p;
+  t.leaf_pivot = b.lf_pivot.p;
+  return t;
+}
+
+// The buffers of one ngt_amd_build_insert call, sized for a batch, and the
+// batch in hand.  res_*: the insertion searches' results, or KNNG's exact
+// E + 1 nearest; list_*: the lists to store, E wide.
+struct InsertCall {
+  ngt_amd_index* ix;
+  BuildState& b;
+  hipStream_t s;
+  uint32_t B, E;
+  const uint32_t* ids = nullptr;  // the batch: n object ids, ascending
+  uint32_t n = 0;
+  DevBuf<uint32_t> d_ids, d_seeds, d_res_ids, d_res_n, d_list_ids, d_list_n, d_dirty, d_vals;
+  DevBuf<uint64_t> d_soff, d_cnt;
+  DevBuf<float> d_res_d, d_list_d, d_pd;
   DevBuf<uint8_t> d_q, d_flag;
-  HIP_OK(d_ids.alloc(B));
-  HIP_OK(d_ri.alloc((size_t)B * K1));
-  HIP_OK(d_rd.alloc((size_t)B * K1));
-  HIP_OK(d_rn.alloc(B));
-  HIP_OK(d_li.alloc((size_t)B * E));
-  HIP_OK(d_ld.alloc((size_t)B * E));
-  HIP_OK(d_ln.alloc(B));
-  HIP_OK(d_flag.alloc(B));
-  std::vector<uint32_t> h_li((size_t)B * E), h_ln(B);
-  std::vector<float> h_ld((size_t)B * E);
-  // NGT_AMD_BUILD_PROFILE=1: per-stage wall time (stream synchronised at each mark)
-  const bool prof = ngt_amd::knob("NGT_AMD_BUILD_PROFILE") != nullptr;
-  double st[3] = {0, 0, 0};
-  auto t_last = std::chrono::steady_clock::now();
-  auto mark = [&](int i) {
-    if (!prof) return;
-    (void)hipStreamSynchronize(s);
-    auto t = std::chrono::steady_clock::now();
-    st[i] += std::chrono::duration<double>(t - t_last).count();
-    t_last = t;
-  };
-  for (size_t pos = 0; pos < todo.size(); pos += B) {
-    const uint32_t n = (uint32_t)std::min<size_t>(B, todo.size() - pos);
-    const uint32_t* ids = todo.data() + pos;
-    if (ensure_tree_capacity(ix, b, 4 * n + 4, n + 1)) return -1;
-    HIP_OK(hipMemcpyAsync(d_ids.p, ids, n * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-    // ---- a. the exact E + 1 nearest: the stored rows are the queries ----------
-    const uint8_t* q = ix->rows.p + (uint64_t)ids[0] * rb;
-    if (ids[n - 1] - ids[0] != n - 1) {  // removed rows in between: the batch's rows side by side
-      HIP_OK(d_q.alloc((size_t)n * rb));
-      HIP_OK(launch_gather_rows(d_q.p, ix->rows.p, rb, d_ids.p, n, s));
-      q = d_q.p;
+  DescentBufs descent;
+  std::vector<uint32_t> h_tseeds, h_tcnt, h_list_ids, h_list_n;
+  std::vector<float> h_list_d;
+  std::vector<uint64_t> h_cnt;
+  hipEvent_t ev_copy = nullptr;  // the lists have reached the host
+  StageClock clk;
+  // NGT_AMD_BUILD_PROFILE: the insertion searches' kernel time and counter sums
+  double k_ms = 0, sum[NGT_AMD_COUNTERS_PER_QUERY] = {}, ex_max = 0, c5_max = 0;
+  uint64_t nsearched = 0;
+
+  InsertCall(ngt_amd_index* i, BuildState& bs)
+      : ix(i), b(bs), s(i->stream), B((uint32_t)bs.batch_size), E((uint32_t)bs.g.edge_size_for_creation) {
+    clk.sync = s;
+  }
+  ~InsertCall() {
+    if (ev_copy) (void)hipEventDestroy(ev_copy);
+  }
+  bool knng() const { return b.g.graph_type == NGT_AMD_GRAPH_KNNG; }
+
+  int alloc() {
+    const uint32_t res_k = knng() ? E + 1 : E;
+    HIP_OK(d_ids.alloc(B));
+    HIP_OK(d_res_ids.alloc((size_t)B * res_k));
+    HIP_OK(d_res_d.alloc((size_t)B * res_k));
+    HIP_OK(d_res_n.alloc(B));
+    HIP_OK(d_list_ids.alloc((size_t)B * E));
+    HIP_OK(d_list_d.alloc((size_t)B * E));
+    HIP_OK(d_list_n.alloc(B));
+    HIP_OK(d_flag.alloc(B));
+    h_list_ids.resize((size_t)B * E);
+    h_list_d.resize((size_t)B * E);
+    h_list_n.resize(B);
+    if (knng()) return 0;  // its rows are queried where they lie; d_q only for a batch with gaps
+    HIP_OK(hipEventCreateWithFlags(&ev_copy, hipEventDisableTiming));
+    HIP_OK(d_q.alloc((size_t)B * ix->row_bytes));
+    if (alloc_descent(descent, B)) return -1;
+    h_tseeds.resize((size_t)B * kTreeSeedStride);
+    h_tcnt.resize(B);
+    if (clk.on) {
+      HIP_OK(d_cnt.alloc((size_t)B * NGT_AMD_COUNTERS_PER_QUERY));
+      h_cnt.resize((size_t)B * NGT_AMD_COUNTERS_PER_QUERY);
     }
-    if (ngt_amd_linear_search_device(ix, q, rb, n, K1, (double)FLT_MAX, d_ri.p, d_rd.p, d_rn.p, s)) return -1;
-    mark(0);
-    // ---- b. moveFrom, the lists, the adjacency rows, the tree flags ------------
-    KnngListArgs ka{};
-    ka.res_ids = d_ri.p;
-    ka.res_dists = d_rd.p;
-    ka.res_n = d_rn.p;
-    ka.K1 = K1;
-    ka.ids = d_ids.p;
-    ka.n = n;
-    ka.out_ids = d_li.p;
-    ka.out_dists = d_ld.p;
-    ka.out_n = d_ln.p;
-    ka.flag = d_flag.p;
-    ka.adj = ix->adj.p;
-    ka.adj_stride = b.adj_stride;
-    HIP_OK(launch_knng_lists(ka, s));
-    HIP_OK(hipMemcpyAsync(h_li.data(), d_li.p, (size_t)n * E * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    HIP_OK(hipMemcpyAsync(h_ld.data(), d_ld.p, (size_t)n * E * sizeof(float), hipMemcpyDeviceToHost, s));
-    HIP_OK(hipMemcpyAsync(h_ln.data(), d_ln.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    // ---- c. DVPTree::insert of the batch, from the root --------------------------
-    HIP_OK(launch_tree_insert(tree_insert_args(ix, b, d_ids.p, d_flag.p, n), ix->metric, ix->otype, s));
-    ix->adj_version++;
-    if (finish_batch(ix, b, s)) return -1;
-    mark(1);
-    // ---- insertKNNGNode (Graph.h:607-609): the graph mirror ----------------------
+    return 0;
+  }
+};
+
+// ---- 1. seeds: all objects of the leaf each batch object descends to; the
+//      same descent locates each object's leaf for step 4.  An empty leaf takes
+//      getSeedsFromGraph's random seeds. -----------------------------------------
+int seed_batch(InsertCall& c, std::vector<uint32_t>& seeds, std::vector<uint64_t>& soff) {
+  const uint32_t n = c.n, SS = kTreeSeedStride;
+  HIP_OK(launch_gather_rows(c.d_q.p, c.ix->rows.p, c.ix->row_bytes, c.d_ids.p, n, c.s));
+  TreeSeedArgs t = tree_descent_args(c.ix, c.b, c.d_q.p, n, c.descent);
+  t.seed_size = (uint32_t)std::max(c.b.seed_size, 0);
+  t.k = c.E;
+  t.all_leaf_nodes = 1;
+  HIP_OK(launch_tree_seeds(t, c.ix->metric, c.ix->otype, c.s));
+  HIP_OK(hipMemcpyAsync(c.h_tseeds.data(), c.descent.tseeds.p, (size_t)n * SS * sizeof(uint32_t),
+                        hipMemcpyDeviceToHost, c.s));
+  HIP_OK(hipMemcpyAsync(c.h_tcnt.data(), c.descent.tcnt.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c.s));
+  HIP_OK(hipStreamSynchronize(c.s));
+  c.clk.mark(0);
+  soff.assign(n + 1, 0);
+  for (uint32_t i = 0; i < n; i++) {
+    seeds.insert(seeds.end(), c.h_tseeds.begin() + (size_t)i * SS, c.h_tseeds.begin() + (size_t)i * SS + c.h_tcnt[i]);
+    if (c.h_tcnt[i] == 0) c.b.g.random_seeds(c.b.rnd, c.b.seed_size, seeds);
+    soff[i + 1] = seeds.size();
+  }
+  return 0;
+}
+
+// ---- 2. insertion searches (searchForNNGInsertion, Index.h:1457-1479) ----------
+int search_batch(InsertCall& c, const std::vector<uint32_t>& seeds, const std::vector<uint64_t>& soff) {
+  const uint32_t n = c.n;
+  if (seeds.empty()) {
+    HIP_OK(hipMemsetAsync(c.d_res_n.p, 0, n * sizeof(uint32_t), c.s));
+    c.clk.mark(1);
+    return 0;
+  }
+  HIP_OK(c.d_seeds.upload(seeds.data(), seeds.size()));
+  HIP_OK(c.d_soff.upload(soff.data(), n + 1));
+  const ngt_amd_search_params p = seeded_search_params(c.E, c.b.epsilon_for_creation, FLT_MAX);
+  if (ngt_amd_search_device(c.ix, &p, c.d_q.p, c.ix->row_bytes, n, c.d_seeds.p, c.d_soff.p, c.d_res_ids.p,
+                            c.d_res_d.p, c.d_res_n.p, c.clk.on ? c.d_cnt.p : nullptr, c.s))
+    return -1;
+  if (c.clk.on) {
+    HIP_OK(hipMemcpyAsync(c.h_cnt.data(), c.d_cnt.p, (size_t)n * NGT_AMD_COUNTERS_PER_QUERY * sizeof(uint64_t),
+                          hipMemcpyDeviceToHost, c.s));
+    HIP_OK(hipStreamSynchronize(c.s));
+    c.k_ms += ngt_amd_last_search_kernel_ms(c.ix);
+    uint64_t mx = 0;
     for (uint32_t i = 0; i < n; i++) {
-      const uint32_t id = ids[i];
-      if (h_ln[i] > E) return fail("ngt_amd_build_insert: a KNNG list of %u entries", h_ln[i]);
-      auto& objs = b.graph[id];
-      objs.resize(h_ln[i]);
-      for (uint32_t j = 0; j < h_ln[i]; j++) objs[j] = {h_li[(size_t)i * E + j], h_ld[(size_t)i * E + j]};
-      b.in_graph[id] = 1;
-      b.graph_size = std::max<uint64_t>(b.graph_size, (uint64_t)id + 1);
+      const uint64_t* q = c.h_cnt.data() + (size_t)i * NGT_AMD_COUNTERS_PER_QUERY;
+      for (int j = 0; j < NGT_AMD_COUNTERS_PER_QUERY; j++) c.sum[j] += (double)q[j];
+      mx = std::max(mx, q[2]);
+      c.c5_max = std::max(c.c5_max, (double)q[5]);
     }
-    mark(2);
+    c.ex_max += (double)mx;
+    c.nsearched += n;
   }
-  if (prof)
-    fprintf(stderr, "build_insert KNNG %zu objects: scan %.3f s, lists + tree insert %.3f s, host graph %.3f s\n",
-            todo.size(), st[0], st[1], st[2]);
+  c.clk.mark(1);
   return 0;
 }
 
-// The reverse edge target <- (id, distance) of insertANNGNode / insertONNGNode:
-// the sorted addEdge with the identity check (Graph.h:845-873).
-int add_edge(BuildState& b, uint32_t target, uint32_t id, float distance, std::vector<uint32_t>& dirty) {
-  auto& node = b.graph[target];
-  const std::pair<uint32_t, float> e{id, distance};
-  auto it = std::lower_bound(node.begin(), node.end(), e, od_less);
-  if (it != node.end() && it->first == id) return fail("NGT::addEdge: already existed! %u:%u", it->first, id);
-  if ((uint64_t)(it - node.begin()) < b.adj_stride) dirty.push_back(target);
-  node.insert(it, e);
+// ---- 3. pairwise distances inside the batch (Index.cpp:690-703), then the
+//      merge / sort / cut of insertMultipleSearchResults (:673-727) ---------------
+int merge_batch(InsertCall& c) {
+  const uint32_t n = c.n;
+  const uint64_t npairs = (uint64_t)n * (n - 1) / 2;
+  if (npairs) HIP_OK(c.d_pd.alloc(npairs));
+  BatchPairArgs bp{};
+  bp.rows = c.ix->rows.p;
+  bp.row_bytes = c.ix->row_bytes;
+  bp.dp = (int)c.ix->dp;
+  bp.batch = c.d_q.p;
+  bp.ids = c.d_ids.p;
+  bp.n = n;
+  bp.out = c.d_pd.p;
+  HIP_OK(launch_batch_pairs(bp, c.ix->metric, c.ix->otype, c.s));
+  BatchMergeArgs bm{};
+  bm.res_ids = c.d_res_ids.p;
+  bm.res_dists = c.d_res_d.p;
+  bm.res_n = c.d_res_n.p;
+  bm.K = c.E;
+  bm.ids = c.d_ids.p;
+  bm.pair = c.d_pd.p;
+  bm.n = n;
+  bm.out_ids = c.d_list_ids.p;
+  bm.out_dists = c.d_list_d.p;
+  bm.out_n = c.d_list_n.p;
+  bm.flag = c.d_flag.p;
+  HIP_OK(launch_batch_merge(bm, c.s));
+  c.clk.mark(2);
   return 0;
 }
 
-// addEdgeDeletingExcessEdges (Graph.h:888-934)
-int add_edge_deleting_excess(BuildState& b, uint32_t target, uint32_t id, float distance,
-                             std::vector<uint32_t>& dirty) {
-  auto& node = b.graph[target];
-  const size_t k_edge = (size_t)b.edge_size_for_creation - 1;
-  if (node.size() > k_edge && node[k_edge].second >= distance) {
-    const std::pair<uint32_t, float> last = node[k_edge];
-    if (last.first >= b.graph.size() || !b.in_graph[last.first])
-      return fail("get: Not in-memory or invalid offset of node. idx=%u size=%zu", last.first, b.graph.size());
-    auto& linked = b.graph[last.first];
-    if (linked.size() > k_edge && last.second >= linked[k_edge].second) {
-      node.erase(node.begin() + k_edge);
-      if (k_edge < b.adj_stride) dirty.push_back(target);
-      const std::pair<uint32_t, float> back{target, last.second};
-      auto it = std::lower_bound(linked.begin(), linked.end(), back, od_less);
-      if (it == linked.end() || it->first != target) {
-        char found[48] = "";
-        if (it != linked.end()) snprintf(found, sizeof found, "%u:", it->first);
-        // the reference prints the edge now at that rank of the shortened list
-        const std::pair<uint32_t, float> now = node.size() > k_edge ? node[k_edge] : std::pair<uint32_t, float>{0u, 0.f};
-        return fail("addEdge: Cannot remove. (b) %u,%u,%u,%g:NGT::removeEdge: Cannot found %s%u", target, id,
-                    now.first, now.second, found, target);
-      }
-      if ((uint64_t)(it - linked.begin()) < b.adj_stride) dirty.push_back(last.first);
-      linked.erase(it);
-    }
+// ---- 4. DVPTree::insert of the batch, behind the lists' copies to the host.
+//      With the leaves step 1 located, the copies are marked by ev_copy: the
+//      host graph work waits for that alone and overlaps the insertion. ---------
+int tree_insert_batch(InsertCall& c, bool located) {
+  const uint32_t n = c.n;
+  TreeBuildArgs ta = tree_insert_args(c.ix, c.b, c.d_ids.p, c.d_flag.p, n);
+  if (located) {
+    ta.pre_leaf = c.descent.pleaf.p;
+    ta.pre_count = c.descent.pcnt.p;
+    ta.pre_dist = c.descent.pdist.p;
   }
-  return add_edge(b, target, id, distance, dirty);
+  HIP_OK(hipMemcpyAsync(c.h_list_ids.data(), c.d_list_ids.p, (size_t)n * c.E * sizeof(uint32_t),
+                        hipMemcpyDeviceToHost, c.s));
+  HIP_OK(hipMemcpyAsync(c.h_list_d.data(), c.d_list_d.p, (size_t)n * c.E * sizeof(float), hipMemcpyDeviceToHost, c.s));
+  HIP_OK(hipMemcpyAsync(c.h_list_n.data(), c.d_list_n.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c.s));
+  if (located) HIP_OK(hipEventRecord(c.ev_copy, c.s));
+  HIP_OK(launch_tree_insert(ta, c.ix->metric, c.ix->otype, c.s));
+  return 0;
+}
+
+// NeighborhoodGraph::insertNode of the batch's objects in id order, from the
+// lists on the host
+int store_lists(InsertCall& c, std::vector<uint32_t>& dirty) {
+  for (uint32_t i = 0; i < c.n; i++) {
+    const uint32_t m = c.h_list_n[i];
+    if (c.knng() && m > c.E) return fail("ngt_amd_build_insert: a KNNG list of %u entries", m);
+    const std::string e = c.b.g.insert_node(c.ids[i], c.h_list_ids.data() + (size_t)i * c.E,
+                                            c.h_list_d.data() + (size_t)i * c.E, m, dirty);
+    if (!e.empty()) return fail("%s", e.c_str());
+  }
+  return 0;
+}
+
+// a batch of an ANNG, IANNG or ONNG: steps 1-4 of the header
+int insert_batch(InsertCall& c) {
+  std::vector<uint32_t> seeds, dirty;
+  std::vector<uint64_t> soff;
+  if (seed_batch(c, seeds, soff) || search_batch(c, seeds, soff) || merge_batch(c) || tree_insert_batch(c, true))
+    return -1;
+  c.clk.mark(4);
+  HIP_OK(hipEventSynchronize(c.ev_copy));
+  if (store_lists(c, dirty)) return -1;
+  c.clk.mark(3);
+  // refresh the padded adjacency of the touched nodes
+  const std::vector<uint32_t> vals = c.b.g.adjacency_rows(dirty);
+  HIP_OK(c.d_dirty.upload(dirty.data(), dirty.size()));
+  HIP_OK(c.d_vals.upload(vals.data(), vals.size()));
+  HIP_OK(launch_adj_scatter(c.ix->adj.p, c.b.g.adj_stride, c.d_dirty.p, c.d_vals.p, (uint32_t)dirty.size(), c.s));
+  c.ix->adj_version++;
+  if (finish_batch(c.ix, c.b, c.s)) return -1;
+  c.clk.mark(5);
+  return 0;
+}
+
+// a batch of a KNNG: steps a-c of the header
+int insert_batch_knng(InsertCall& c) {
+  ngt_amd_index* ix = c.ix;
+  const uint32_t n = c.n, K1 = c.E + 1;
+  const uint64_t rb = ix->row_bytes;
+  // ---- a. the exact E + 1 nearest: the stored rows are the queries ------------
+  const uint8_t* q = ix->rows.p + (uint64_t)c.ids[0] * rb;
+  if (c.ids[n - 1] - c.ids[0] != n - 1) {  // removed rows in between: the batch's rows side by side
+    HIP_OK(c.d_q.alloc((size_t)n * rb));
+    HIP_OK(launch_gather_rows(c.d_q.p, ix->rows.p, rb, c.d_ids.p, n, c.s));
+    q = c.d_q.p;
+  }
+  if (ngt_amd_linear_search_device(ix, q, rb, n, K1, (double)FLT_MAX, c.d_res_ids.p, c.d_res_d.p, c.d_res_n.p, c.s))
+    return -1;
+  c.clk.mark(0);
+  // ---- b. moveFrom, the lists, the adjacency rows, the tree flags --------------
+  KnngListArgs ka{};
+  ka.res_ids = c.d_res_ids.p;
+  ka.res_dists = c.d_res_d.p;
+  ka.res_n = c.d_res_n.p;
+  ka.K1 = K1;
+  ka.ids = c.d_ids.p;
+  ka.n = n;
+  ka.out_ids = c.d_list_ids.p;
+  ka.out_dists = c.d_list_d.p;
+  ka.out_n = c.d_list_n.p;
+  ka.flag = c.d_flag.p;
+  ka.adj = ix->adj.p;
+  ka.adj_stride = c.b.g.adj_stride;
+  HIP_OK(launch_knng_lists(ka, c.s));
+  // ---- c. DVPTree::insert of the batch, from the root ----------------------------
+  if (tree_insert_batch(c, false)) return -1;
+  ix->adj_version++;
+  if (finish_batch(ix, c.b, c.s)) return -1;
+  c.clk.mark(1);
+  std::vector<uint32_t> dirty;  // stays empty: the kernel wrote the adjacency rows
+  if (store_lists(c, dirty)) return -1;
+  c.clk.mark(2);
+  return 0;
 }
 
 }  // namespace
@@ -377,268 +560,36 @@ extern "C" int ngt_amd_build_insert(ngt_amd_index* ix, uint64_t first_id, uint64
   // changing: build_begin set max_degree = adj_stride, so the copy always
   // holds every edge they read
   BuildState& b = *ix->build;
-  hipStream_t s = ix->stream;
-  const uint64_t rb = ix->row_bytes;
   if (end_id > ix->nrows) end_id = ix->nrows;
   if (first_id < 1) first_id = 1;
   std::vector<uint32_t> todo;
   for (uint64_t id = first_id; id < end_id; id++)
-    if (ix->h_valid[id] && !b.in_graph[id]) todo.push_back((uint32_t)id);
-  if (b.graph_type == NGT_AMD_GRAPH_KNNG) return insert_knng(ix, b, todo);
-
-  const uint32_t B = (uint32_t)b.batch_size, K = (uint32_t)b.edge_size_for_creation;
-  struct Ev {
-    hipEvent_t e = nullptr;
-    ~Ev() {
-      if (e) (void)hipEventDestroy(e);
-    }
-  } ev_copy;
-  HIP_OK(hipEventCreateWithFlags(&ev_copy.e, hipEventDisableTiming));
-  const uint32_t SS = kTreeSeedStride;
-  DevBuf<uint32_t> d_ids, d_tseeds, d_tcnt, d_seeds, d_oi, d_on, d_dirty, d_vals;
-  DevBuf<uint64_t> d_soff;
-  DevBuf<float> d_od, d_pd;
-  DevBuf<uint8_t> d_q, d_flag;
-  HIP_OK(d_ids.alloc(B));
-  HIP_OK(d_q.alloc((size_t)B * rb));
-  HIP_OK(d_tseeds.alloc((size_t)B * SS));
-  HIP_OK(d_tcnt.alloc(B));
-  HIP_OK(d_oi.alloc((size_t)B * K));
-  HIP_OK(d_od.alloc((size_t)B * K));
-  HIP_OK(d_on.alloc(B));
-  HIP_OK(d_flag.alloc(B));
-  DevBuf<uint32_t> d_pleaf, d_pcnt;
-  DevBuf<float> d_pdist;
-  HIP_OK(d_pleaf.alloc(B));
-  HIP_OK(d_pcnt.alloc(B));
-  HIP_OK(d_pdist.alloc(B));
-  DevBuf<uint32_t> d_mi, d_mn;
-  DevBuf<float> d_md;
-  HIP_OK(d_mi.alloc((size_t)B * K));
-  HIP_OK(d_md.alloc((size_t)B * K));
-  HIP_OK(d_mn.alloc(B));
-  std::vector<uint32_t> h_tseeds((size_t)B * SS), h_tcnt(B), h_mi((size_t)B * K), h_mn(B);
-  std::vector<float> h_md((size_t)B * K);
-  // NGT_AMD_BUILD_PROFILE=1: per-stage wall time (stream synchronised at each mark)
-  const bool prof = ngt_amd::knob("NGT_AMD_BUILD_PROFILE") != nullptr;
-  double st[6] = {0, 0, 0, 0, 0, 0};
-  auto t_last = std::chrono::steady_clock::now();
-  DevBuf<uint64_t> d_cnt;
-  std::vector<uint64_t> h_cnt;
-  double k_ms = 0, dc = 0, ex = 0, ex_max = 0, c3 = 0, c5 = 0, c6 = 0, c7 = 0, c5_max = 0;
-  uint64_t nsearched = 0;
-  if (prof) {
-    HIP_OK(d_cnt.alloc((size_t)B * NGT_AMD_COUNTERS_PER_QUERY));
-    h_cnt.resize((size_t)B * NGT_AMD_COUNTERS_PER_QUERY);
+    if (ix->h_valid[id] && !b.g.in_graph[id]) todo.push_back((uint32_t)id);
+  InsertCall c(ix, b);
+  if (c.alloc()) return -1;
+  for (size_t pos = 0; pos < todo.size(); pos += c.B) {
+    c.ids = todo.data() + pos;
+    c.n = (uint32_t)std::min<size_t>(c.B, todo.size() - pos);
+    if (ensure_tree_capacity(ix, b, 4 * c.n + 4, c.n + 1)) return -1;
+    HIP_OK(hipMemcpyAsync(c.d_ids.p, c.ids, c.n * sizeof(uint32_t), hipMemcpyHostToDevice, c.s));
+    if (c.knng() ? insert_batch_knng(c) : insert_batch(c)) return -1;
   }
-  auto mark = [&](int i) {
-    if (!prof) return;
-    (void)hipStreamSynchronize(s);
-    auto t = std::chrono::steady_clock::now();
-    st[i] += std::chrono::duration<double>(t - t_last).count();
-    t_last = t;
-  };
-
-  for (size_t pos = 0; pos < todo.size(); pos += B) {
-    const uint32_t n = (uint32_t)std::min<size_t>(B, todo.size() - pos);
-    const uint32_t* ids = todo.data() + pos;
-    if (ensure_tree_capacity(ix, b, 4 * n + 4, n + 1)) return -1;
-    HIP_OK(hipMemcpyAsync(d_ids.p, ids, n * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-    HIP_OK(launch_gather_rows(d_q.p, ix->rows.p, rb, d_ids.p, n, s));
-
-    // ---- 1. seeds: all objects of the leaf each batch object descends to --
-    TreeSeedArgs t{};
-    t.queries = d_q.p;
-    t.query_bytes = rb;
-    t.nq = n;
-    t.dp = (int)ix->dp;
-    t.row_bytes = rb;
-    t.in_pivot = b.in_pivot.p;
-    t.in_child = b.in_child.p;
-    t.in_border = b.in_border.p;
-    t.children = 5;
-    t.root = b.root;
-    t.leaf_count = b.lf_count.p;
-    t.leaf_stride = kLeafCap;
-    t.leaf_ids = b.lf_ids.p;
-    t.seed_size = (uint32_t)std::max(b.seed_size, 0);
-    t.k = K;
-    t.all_leaf_nodes = 1;
-    t.seeds = d_tseeds.p;
-    t.seed_stride = SS;
-    t.seed_count = d_tcnt.p;
-    // the same descent locates each object's leaf for step 4
-    t.out_leaf = d_pleaf.p;
-    t.out_count = d_pcnt.p;
-    t.out_pdist = d_pdist.p;
-    t.leaf_pivot = b.lf_pivot.p;
-    HIP_OK(launch_tree_seeds(t, ix->metric, ix->otype, s));
-    HIP_OK(hipMemcpyAsync(h_tseeds.data(), d_tseeds.p, (size_t)n * SS * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    HIP_OK(hipMemcpyAsync(h_tcnt.data(), d_tcnt.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    HIP_OK(hipStreamSynchronize(s));
-    mark(0);
-    std::vector<uint32_t> seeds;
-    std::vector<uint64_t> soff(n + 1, 0);
-    for (uint32_t i = 0; i < n; i++) {
-      const size_t start = seeds.size();
-      for (uint32_t j = 0; j < h_tcnt[i]; j++) seeds.push_back(h_tseeds[(size_t)i * SS + j]);
-      if (h_tcnt[i] == 0 && b.graph_size != 0) {
-        // getSeedsFromGraph -> getRandomSeeds (Index.h:775-801, 1115-1135)
-        const size_t repo = b.graph_size - 1;
-        const size_t ss = std::min<size_t>(repo, (size_t)std::max(b.seed_size, 0));
-        size_t empty = 0;
-        while (seeds.size() - start < ss) {
-          const double r = ((double)b.rnd.next() + 1.0) / ((double)2147483647 + 2.0);
-          const size_t idx = (size_t)floor((double)repo * r) + 1;
-          if (!b.in_graph[idx]) {
-            if (++empty > repo) break;
-            continue;
-          }
-          if (std::find(seeds.begin() + start, seeds.end(), (uint32_t)idx) != seeds.end()) continue;
-          seeds.push_back((uint32_t)idx);
-        }
-      }
-      soff[i + 1] = seeds.size();
-    }
-
-    // ---- 2. insertion searches (searchForNNGInsertion, Index.h:1457-1479) --
-    if (!seeds.empty()) {
-      HIP_OK(d_seeds.upload(seeds.data(), seeds.size()));
-      HIP_OK(d_soff.upload(soff.data(), n + 1));
-      ngt_amd_search_params p{};
-      p.k = K;
-      p.epsilon = b.epsilon_for_creation;
-      p.radius = FLT_MAX;
-      p.edge_size = -1;  // sc.edgeSize default -> edgeSizeForSearch
-      p.seed_mode = NGT_AMD_SEED_GIVEN;
-      p.visited_hash_log2 = 0;
-      if (ngt_amd_search_device(ix, &p, d_q.p, rb, n, d_seeds.p, d_soff.p, d_oi.p, d_od.p, d_on.p,
-                                prof ? d_cnt.p : nullptr, s))
-        return -1;
-      if (prof) {
-        HIP_OK(hipMemcpyAsync(h_cnt.data(), d_cnt.p, (size_t)n * NGT_AMD_COUNTERS_PER_QUERY * sizeof(uint64_t),
-                              hipMemcpyDeviceToHost, s));
-        HIP_OK(hipStreamSynchronize(s));
-        k_ms += ngt_amd_last_search_kernel_ms(ix);
-        uint64_t mx = 0;
-        for (uint32_t i = 0; i < n; i++) {
-          dc += (double)h_cnt[(size_t)i * NGT_AMD_COUNTERS_PER_QUERY];
-          ex += (double)h_cnt[(size_t)i * NGT_AMD_COUNTERS_PER_QUERY + 2];
-          mx = std::max(mx, h_cnt[(size_t)i * NGT_AMD_COUNTERS_PER_QUERY + 2]);
-          const uint64_t* c = h_cnt.data() + (size_t)i * NGT_AMD_COUNTERS_PER_QUERY;
-          c3 += (double)c[3];
-          c5 += (double)c[5];
-          c6 += (double)c[6];
-          c7 += (double)c[7];
-          c5_max = std::max(c5_max, (double)c[5]);
-        }
-        ex_max += (double)mx;
-        nsearched += n;
-      }
-    } else {
-      HIP_OK(hipMemsetAsync(d_on.p, 0, n * sizeof(uint32_t), s));
-    }
-    mark(1);
-
-    // ---- 3. pairwise distances inside the batch (Index.cpp:690-703), then the
-    //         merge / sort / cut of insertMultipleSearchResults (:673-727) -------
-    const uint64_t npairs = (uint64_t)n * (n - 1) / 2;
-    if (npairs) HIP_OK(d_pd.alloc(npairs));
-    BatchPairArgs bp{};
-    bp.rows = ix->rows.p;
-    bp.row_bytes = rb;
-    bp.dp = (int)ix->dp;
-    bp.batch = d_q.p;
-    bp.ids = d_ids.p;
-    bp.n = n;
-    bp.out = d_pd.p;
-    HIP_OK(launch_batch_pairs(bp, ix->metric, ix->otype, s));
-    BatchMergeArgs bm{};
-    bm.res_ids = d_oi.p;
-    bm.res_dists = d_od.p;
-    bm.res_n = d_on.p;
-    bm.K = K;
-    bm.ids = d_ids.p;
-    bm.pair = d_pd.p;
-    bm.n = n;
-    bm.out_ids = d_mi.p;
-    bm.out_dists = d_md.p;
-    bm.out_n = d_mn.p;
-    bm.flag = d_flag.p;
-    HIP_OK(launch_batch_merge(bm, s));
-    mark(2);
-
-    // ---- 4. DVPTree::insert of the batch (device, overlaps the host graph work)
-    TreeBuildArgs ta = tree_insert_args(ix, b, d_ids.p, d_flag.p, n);
-    ta.pre_leaf = d_pleaf.p;
-    ta.pre_count = d_pcnt.p;
-    ta.pre_dist = d_pdist.p;
-    // the merged lists go to the host while the tree insertion runs
-    HIP_OK(hipMemcpyAsync(h_mi.data(), d_mi.p, (size_t)n * K * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    HIP_OK(hipMemcpyAsync(h_md.data(), d_md.p, (size_t)n * K * sizeof(float), hipMemcpyDeviceToHost, s));
-    HIP_OK(hipMemcpyAsync(h_mn.data(), d_mn.p, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    HIP_OK(hipEventRecord(ev_copy.e, s));
-    HIP_OK(launch_tree_insert(ta, ix->metric, ix->otype, s));
-    mark(4);
-    HIP_OK(hipEventSynchronize(ev_copy.e));
-
-    // ---- insertANNGNode (Graph.h:611-625): the node, then the reverse edges;
-    //      insertIANNGNode (:628-635) and insertONNGNode (:637-655) likewise ------
-    std::vector<uint32_t> dirty;
-    for (uint32_t i = 0; i < n; i++) {
-      const uint32_t id = ids[i];
-      auto& objs = b.graph[id];
-      objs.resize(h_mn[i]);
-      for (uint32_t j = 0; j < h_mn[i]; j++) objs[j] = {h_mi[(size_t)i * K + j], h_md[(size_t)i * K + j]};
-      b.in_graph[id] = 1;
-      b.graph_size = std::max<uint64_t>(b.graph_size, (uint64_t)id + 1);
-      dirty.push_back(id);
-      if (b.graph_type == NGT_AMD_GRAPH_IANNG) {
-        // the job's results, not the stored list: a deletion may shorten that one
-        const std::vector<std::pair<uint32_t, float>> results(objs);
-        for (const auto& r : results)
-          if (add_edge_deleting_excess(b, r.first, id, r.second, dirty)) return -1;
-      } else if (b.graph_type == NGT_AMD_GRAPH_ONNG) {
-        const size_t in = std::min<size_t>(objs.size(), (size_t)b.incoming_edge);
-        for (size_t j = 0; j < in; j++)
-          if (add_edge(b, objs[j].first, id, objs[j].second, dirty)) return -1;
-        if (objs.size() > (size_t)b.outgoing_edge) objs.resize(b.outgoing_edge);
-      } else {
-        for (const auto& r : objs)
-          if (add_edge(b, r.first, id, r.second, dirty)) return -1;
-      }
-    }
-    mark(3);
-
-    // ---- refresh the padded adjacency of the touched nodes -----------------
-    std::sort(dirty.begin(), dirty.end());
-    dirty.erase(std::unique(dirty.begin(), dirty.end()), dirty.end());
-    std::vector<uint32_t> vals(dirty.size() * b.adj_stride, 0u);
-    for (size_t i = 0; i < dirty.size(); i++) {
-      const auto& node = b.graph[dirty[i]];
-      const size_t m = std::min<size_t>(node.size(), b.adj_stride);
-      for (size_t j = 0; j < m; j++) vals[i * b.adj_stride + j] = node[j].first;
-    }
-    HIP_OK(d_dirty.upload(dirty.data(), dirty.size()));
-    HIP_OK(d_vals.upload(vals.data(), vals.size()));
-    HIP_OK(launch_adj_scatter(ix->adj.p, b.adj_stride, d_dirty.p, d_vals.p, (uint32_t)dirty.size(), s));
-    ix->adj_version++;
-    if (finish_batch(ix, b, s)) return -1;
-    mark(5);
+  if (!c.clk.on) return 0;
+  const double* st = c.clk.st;
+  if (c.knng()) {
+    fprintf(stderr, "build_insert KNNG %zu objects: scan %.3f s, lists + tree insert %.3f s, host graph %.3f s\n",
+            todo.size(), st[0], st[1], st[2]);
+    return 0;
   }
-  if (prof)
-    fprintf(stderr, "build_insert %zu objects: seeds %.3f s, search %.3f s, pairs+merge %.3f s, host graph %.3f s, "
-            "tree insert %.3f s, adjacency %.3f s; search kernel %.3f s, per query %.1f distances %.1f expansions, "
-            "mean per-batch max expansions %.1f\n", todo.size(), st[0], st[1], st[2], st[3], st[4], st[5], k_ms / 1e3,
-            dc / std::max<uint64_t>(nsearched, 1), ex / std::max<uint64_t>(nsearched, 1),
-            ex_max / std::max<double>(1.0, (double)((todo.size() + B - 1) / B)));
-  if (prof) {
-    const double nq = (double)std::max<uint64_t>(nsearched, 1);
-    // counters [3], [5..7]: spilled-visited flag, max unchecked, 0, 0 -- or, in
-    // the NGT_AMD_STAMPS build, rest/pop/adjacency/eval cycles
-    fprintf(stderr, "build_insert counters per query: c3 %.4g c5 %.4g (max %.4g) c6 %.4g c7 %.4g\n", c3 / nq,
-            c5 / nq, c5_max, c6 / nq, c7 / nq);
-  }
+  const double nq = (double)std::max<uint64_t>(c.nsearched, 1);
+  fprintf(stderr, "build_insert %zu objects: seeds %.3f s, search %.3f s, pairs+merge %.3f s, host graph %.3f s, "
+          "tree insert %.3f s, adjacency %.3f s; search kernel %.3f s, per query %.1f distances %.1f expansions, "
+          "mean per-batch max expansions %.1f\n", todo.size(), st[0], st[1], st[2], st[3], st[4], st[5], c.k_ms / 1e3,
+          c.sum[0] / nq, c.sum[2] / nq, c.ex_max / std::max<double>(1.0, (double)((todo.size() + c.B - 1) / c.B)));
+  // counters [3], [5..7]: spilled-visited flag, max unchecked, 0, 0 -- or, in
+  // the NGT_AMD_STAMPS build, rest/pop/adjacency/eval cycles
+  fprintf(stderr, "build_insert counters per query: c3 %.4g c5 %.4g (max %.4g) c6 %.4g c7 %.4g\n", c.sum[3] / nq,
+          c.sum[5] / nq, c.c5_max, c.sum[6] / nq, c.sum[7] / nq);
   return 0;
 }
 
@@ -648,23 +599,12 @@ extern "C" int ngt_amd_build_set_graph(ngt_amd_index* ix, const uint64_t* offset
   if (offsets[graph_rows] && (!ids || !dists)) return fail("ngt_amd_build_set_graph: bad arguments");
   HIP_OK(hipSetDevice(ix->device));
   ServeHold serve_hold(ix);
-  BuildState& b = *ix->build;
-  const uint64_t S = b.adj_stride;
-  std::vector<uint32_t> adj((size_t)ix->nrows * S, 0u);
-  b.graph_size = 0;
-  b.node_rows = graph_rows;
-  for (uint64_t v = 0; v < graph_rows; v++) {
-    const uint64_t e0 = offsets[v], e1 = offsets[v + 1];
-    auto& node = b.graph[v];
-    node.clear();
-    for (uint64_t e = e0; e < e1; e++) {
-      if (ids[e] == 0 || ids[e] >= ix->nrows) return fail("ngt_amd_build_set_graph: edge %u out of range", ids[e]);
-      node.push_back({ids[e], dists[e]});
-      if (e - e0 < S) adj[(size_t)v * S + (e - e0)] = ids[e];
-    }
-    b.in_graph[v] = e1 > e0 ? 1 : 0;
-    if (e1 > e0) b.graph_size = v + 1;
-  }
+  SessionGraph& g = ix->build->g;
+  const std::string e = g.set_csr(offsets, ids, dists, graph_rows);
+  if (!e.empty()) return fail("%s", e.c_str());
+  std::vector<uint32_t> every(ix->nrows);
+  for (uint64_t v = 0; v < ix->nrows; v++) every[v] = (uint32_t)v;
+  const std::vector<uint32_t> adj = g.adjacency_rows(every);
   HIP_OK(hipMemcpy(ix->adj.p, adj.data(), adj.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
   ix->adj_version++;
   return 0;
@@ -765,11 +705,6 @@ int relink(ngt_amd_index* ix, RemoveScratch& sc, const uint32_t* nbr, uint32_t d
   return 0;
 }
 
-// a graph node exists: it has edges, or it lost them all to earlier removals
-bool has_node(const ngt_amd_index* ix, const BuildState& b, uint32_t id) {
-  return b.in_graph[id] || (ix->h_valid[id] && id < b.node_rows);
-}
-
 int drop_object(ngt_amd_index* ix, uint32_t id) {
   const uint8_t zero = 0;
   ix->h_valid[id] = 0;
@@ -778,132 +713,15 @@ int drop_object(ngt_amd_index* ix, uint32_t id) {
   return 0;
 }
 
-// 0 removed, 1 no such object, 2 refused (nothing changed), -1 device failure
-// st (nullable): seconds spent enqueueing, waiting, on the leaf, on the lists, on the adjacency
-int remove_one(ngt_amd_index* ix, BuildState& b, RemoveScratch& sc, uint32_t id, double* st) {
-  auto t_last = std::chrono::steady_clock::now();
-  auto mark = [&](int i) {
-    if (!st) return;
-    auto t = std::chrono::steady_clock::now();
-    st[i] += std::chrono::duration<double>(t - t_last).count();
-    t_last = t;
-  };
-  hipStream_t s = ix->stream;
-  const uint64_t rb = ix->row_bytes;
-  if (id == 0 || id >= ix->nrows || !ix->h_valid[id]) {
-    fail("get: Not in-memory or invalid offset of node. idx=%u size=%llu", id, (unsigned long long)ix->nrows);
-    return 1;
-  }
-  if (!has_node(ix, b, id)) return drop_object(ix, id);  // Index.h:1411-1422
+// a removal refused before anything changed
+int refuse(const std::string& why) {
+  fail("%s", why.c_str());
+  return 2;
+}
 
-  // The reference's search throws when it evaluates a neighbour whose object
-  // is gone (Graph.cpp:603; a directed graph keeps edges to removed nodes),
-  // which refuses the id before anything changes: the same test on the lists
-  // the search expands -- the node's own and, below, its duplicate's.
-  auto evaluated_edges_exist = [&](uint32_t v) {
-    const auto& n = b.graph[v];
-    const size_t lim = b.edge_size_for_search <= 0 ? n.size() : std::min<size_t>(n.size(), b.edge_size_for_search);
-    for (size_t j = 0; j < lim; j++)
-      if (n[j].first >= ix->nrows || !ix->h_valid[n[j].first]) {
-        fail("get: Not in-memory or invalid offset of node. idx=%u size=%llu", n[j].first,
-             (unsigned long long)ix->nrows);
-        return false;
-      }
-    return true;
-  };
-  if (!evaluated_edges_exist(id)) return 2;
-
-  // ---- the neighbours to relink (nothing is edited before every check) -----
-  std::vector<uint32_t> nbr;
-  std::vector<float> nbr_d;
-  for (const auto& e : b.graph[id]) {
-    if (e.first == id) continue;  // a self edge is erased
-    if (e.first >= ix->nrows || !ix->h_valid[e.first] || !has_node(ix, b, e.first)) {
-      fail("removeEdgesReliably : Relink error ID=%u: neighbour %u has no object or no node", id, e.first);
-      return 2;
-    }
-    nbr.push_back(e.first);
-    nbr_d.push_back(e.second);
-  }
-  const uint32_t d = (uint32_t)nbr.size();
-  if (d > removal::kMaxList) {
-    fail("ngt_amd_build_remove: node %u has %u neighbours, more than the supported %u", id, d, removal::kMaxList);
-    return 2;
-  }
-
-  // ---- the duplicate search (Index.h:1423-1432) ---------------------------
-  const uint8_t* d_row = ix->rows.p + (uint64_t)id * rb;
-  const uint64_t soff[2] = {0, 1};
-  HIP_OK(sc.seed.upload_async(&id, 1, s));
-  HIP_OK(sc.soff.upload_async(soff, 2, s));
-  HIP_OK(sc.oi.alloc(2));
-  HIP_OK(sc.od.alloc(2));
-  HIP_OK(sc.on.alloc(1));
-  ngt_amd_search_params p{};
-  p.k = 2;
-  p.epsilon = 0.1f;
-  p.radius = 0.0f;
-  p.edge_size = -1;
-  p.seed_mode = NGT_AMD_SEED_GIVEN;
-  p.visited_hash_log2 = 0;
-  if (ngt_amd_search_device(ix, &p, d_row, rb, 1, sc.seed.p, sc.soff.p, sc.oi.p, sc.od.p, sc.on.p, nullptr, s))
-    return -1;
-  uint32_t found[2] = {0, 0}, nfound = 0;
-  HIP_OK(hipMemcpyAsync(found, sc.oi.p, sizeof found, hipMemcpyDeviceToHost, s));
-  HIP_OK(hipMemcpyAsync(&nfound, sc.on.p, sizeof nfound, hipMemcpyDeviceToHost, s));
-
-  // ---- the descent to the object's leaf (Tree.h:156-176) and the relink
-  //      chain of the neighbours, behind the search on the same stream: the
-  //      three need nothing from one another, so one wait serves them all ----
-  TreeSeedArgs t{};
-  HIP_OK(sc.tseeds.alloc(kTreeSeedStride));
-  HIP_OK(sc.tcnt.alloc(1));
-  HIP_OK(sc.pleaf.alloc(1));
-  HIP_OK(sc.pcnt.alloc(1));
-  HIP_OK(sc.pdist.alloc(1));
-  t.queries = d_row;
-  t.query_bytes = rb;
-  t.nq = 1;
-  t.dp = (int)ix->dp;
-  t.row_bytes = rb;
-  t.in_pivot = b.in_pivot.p;
-  t.in_child = b.in_child.p;
-  t.in_border = b.in_border.p;
-  t.children = 5;
-  t.root = b.root;
-  t.leaf_count = b.lf_count.p;
-  t.leaf_stride = kLeafCap;
-  t.leaf_ids = b.lf_ids.p;
-  t.seed_size = 1;
-  t.k = 1;
-  t.all_leaf_nodes = 0;
-  t.seeds = sc.tseeds.p;
-  t.seed_stride = kTreeSeedStride;
-  t.seed_count = sc.tcnt.p;
-  t.out_leaf = sc.pleaf.p;
-  t.out_count = sc.pcnt.p;
-  t.out_pdist = sc.pdist.p;
-  t.leaf_pivot = b.lf_pivot.p;
-  HIP_OK(launch_tree_seeds(t, ix->metric, ix->otype, s));
-  uint32_t leaf = 0, cnt = 0;
-  HIP_OK(hipMemcpyAsync(&leaf, sc.pleaf.p, sizeof leaf, hipMemcpyDeviceToHost, s));
-  HIP_OK(hipMemcpyAsync(&cnt, sc.pcnt.p, sizeof cnt, hipMemcpyDeviceToHost, s));
-  std::vector<uint32_t> la(d ? d - 1 : 0), lb(d ? d - 1 : 0);
-  std::vector<float> ld(d ? d - 1 : 0);
-  if (relink(ix, sc, nbr.data(), d, la.data(), lb.data(), ld.data(), false)) return -1;
-  int serr = 0;
-  mark(0);
-  if (take_device_error(ix, s, &serr)) return -1;
-  if (serr) return fail("ngt_amd_build_remove: device error flag %d in the duplicate search", serr);
-  if (nfound == 0) {
-    fail("Not found the specified id");
-    return 2;
-  }
-  const uint32_t replace_id = nfound == 1 ? 0u : (found[0] == id ? found[1] : found[0]);
-  if (replace_id != 0 && (replace_id >= ix->nrows || !evaluated_edges_exist(replace_id))) return 2;
-
-  mark(1);
-  // ---- DVPTree::remove / replace (Tree.h:178-202, Node.cpp:229-280) --------
+// DVPTree::remove / replace (Tree.h:178-202, Node.cpp:229-280) on the leaf the
+// object descended to: 0 done, 2 refused, -1 device failure
+int edit_leaf(BuildState& b, uint32_t id, uint32_t replace_id, uint32_t leaf, uint32_t cnt) {
   if (leaf == 0 || leaf >= b.n_leaf || cnt >= kLeafCap)
     return fail("ngt_amd_build_remove: the tree descent of %u ended at leaf %u with %u objects", id, leaf, cnt);
   uint32_t lids[kLeafCap];
@@ -918,69 +736,121 @@ int remove_one(ngt_amd_index* ix, BuildState& b, RemoveScratch& sc, uint32_t id,
     // the duplicate takes the leaf entry; a leaf without the entry is ignored (Index.h:1448-1452)
     if (at < cnt)
       HIP_OK(hipMemcpy(b.lf_ids.p + (size_t)leaf * kLeafCap + at, &replace_id, sizeof(uint32_t), hipMemcpyHostToDevice));
-  } else {
-    if (at == cnt) {
-      fail("remove:: cannot remove from tree. id=%u VpTree::remove: Inner error. Cannot remove object. leafNode=%u:"
-           "VpTree::Leaf::remove: Warning. Cannot find the specified object. ID=%u,0 idx=%u If the same objects "
-           "were inserted into the index, ignore this message.", id, leaf, id, at);
-      return 2;
-    }
-    for (uint32_t j = at; j + 1 < cnt; j++) {
-      lids[j] = lids[j + 1];
-      ldst[j] = ldst[j + 1];
-    }
-    cnt--;
-    if (cnt > at) {
-      HIP_OK(hipMemcpy(b.lf_ids.p + (size_t)leaf * kLeafCap + at, lids + at, (cnt - at) * sizeof(uint32_t),
-                       hipMemcpyHostToDevice));
-      HIP_OK(hipMemcpy(b.lf_dist.p + (size_t)leaf * kLeafCap + at, ldst + at, (cnt - at) * sizeof(float),
-                       hipMemcpyHostToDevice));
-    }
-    HIP_OK(hipMemcpy(b.lf_count.p + leaf, &cnt, sizeof(uint32_t), hipMemcpyHostToDevice));
-    // an emptied leaf stays in place; the collapse of an all-empty subtree
-    // (removeEmptyNodes, Tree.cpp:338-397) is not reproduced
+    return 0;
+  }
+  if (at == cnt) {
+    fail("remove:: cannot remove from tree. id=%u VpTree::remove: Inner error. Cannot remove object. leafNode=%u:"
+         "VpTree::Leaf::remove: Warning. Cannot find the specified object. ID=%u,0 idx=%u If the same objects "
+         "were inserted into the index, ignore this message.", id, leaf, id, at);
+    return 2;
+  }
+  for (uint32_t j = at; j + 1 < cnt; j++) {
+    lids[j] = lids[j + 1];
+    ldst[j] = ldst[j + 1];
+  }
+  cnt--;
+  if (cnt > at) {
+    HIP_OK(hipMemcpy(b.lf_ids.p + (size_t)leaf * kLeafCap + at, lids + at, (cnt - at) * sizeof(uint32_t),
+                     hipMemcpyHostToDevice));
+    HIP_OK(hipMemcpy(b.lf_dist.p + (size_t)leaf * kLeafCap + at, ldst + at, (cnt - at) * sizeof(float),
+                     hipMemcpyHostToDevice));
+  }
+  HIP_OK(hipMemcpy(b.lf_count.p + leaf, &cnt, sizeof(uint32_t), hipMemcpyHostToDevice));
+  // an emptied leaf stays in place; the collapse of an all-empty subtree
+  // (removeEmptyNodes, Tree.cpp:338-397) is not reproduced
+  return 0;
+}
+
+// 0 removed, 1 no such object, 2 refused (nothing changed), -1 device failure
+// clk: seconds spent enqueueing, waiting, on the leaf, on the lists, on the adjacency
+int remove_one(ngt_amd_index* ix, BuildState& b, RemoveScratch& sc, uint32_t id, StageClock& clk) {
+  clk.start();
+  SessionGraph& g = b.g;
+  hipStream_t s = ix->stream;
+  const uint64_t rb = ix->row_bytes;
+  if (id == 0 || id >= ix->nrows || !ix->h_valid[id]) {
+    fail("get: Not in-memory or invalid offset of node. idx=%u size=%llu", id, (unsigned long long)ix->nrows);
+    return 1;
+  }
+  if (!g.has_node(ix->h_valid, id)) return drop_object(ix, id);  // Index.h:1411-1422
+
+  // Nothing is edited before every check: the lists the duplicate search
+  // expands -- the node's own and, below, its duplicate's -- and the
+  // neighbours to relink.
+  std::string e = g.evaluated_edges_exist(ix->h_valid, id, b.edge_size_for_search);
+  if (!e.empty()) return refuse(e);
+  std::vector<uint32_t> nbr;
+  std::vector<float> nbr_d;
+  e = g.removal_neighbours(ix->h_valid, id, nbr, nbr_d);
+  if (!e.empty()) return refuse(e);
+  const uint32_t d = (uint32_t)nbr.size();
+  if (d > removal::kMaxList) {
+    fail("ngt_amd_build_remove: node %u has %u neighbours, more than the supported %u", id, d, removal::kMaxList);
+    return 2;
   }
 
-  mark(2);
-  // ---- removeEdgesReliably on the host lists --------------------------------
-  for (uint32_t i = 0; i < d; i++) {
-    auto& n = b.graph[nbr[i]];
-    const std::pair<uint32_t, float> e{id, nbr_d[i]};
-    auto it = std::lower_bound(n.begin(), n.end(), e, od_less);
-    if (it != n.end() && it->first == id) n.erase(it);  // else "cannot find an edge ... anyway continue"
-  }
-  for (uint32_t i = 0; i + 1 < d; i++) {
-    auto link = [&](uint32_t from, uint32_t to) {
-      auto& n = b.graph[from];
-      const std::pair<uint32_t, float> e{to, ld[i]};
-      auto it = std::lower_bound(n.begin(), n.end(), e, od_less);
-      if (it == n.end() || it->first != to) n.insert(it, e);
-    };
-    link(la[i], lb[i]);
-    link(lb[i], la[i]);
-  }
-  b.graph[id].clear();
-  b.in_graph[id] = 0;
+  // ---- the duplicate search (Index.h:1423-1432) ---------------------------
+  const uint8_t* d_row = ix->rows.p + (uint64_t)id * rb;
+  const uint64_t soff[2] = {0, 1};
+  HIP_OK(sc.seed.upload_async(&id, 1, s));
+  HIP_OK(sc.soff.upload_async(soff, 2, s));
+  HIP_OK(sc.oi.alloc(2));
+  HIP_OK(sc.od.alloc(2));
+  HIP_OK(sc.on.alloc(1));
+  const ngt_amd_search_params p = seeded_search_params(2, 0.1f, 0.0f);
+  if (ngt_amd_search_device(ix, &p, d_row, rb, 1, sc.seed.p, sc.soff.p, sc.oi.p, sc.od.p, sc.on.p, nullptr, s))
+    return -1;
+  uint32_t found[2] = {0, 0}, nfound = 0;
+  HIP_OK(hipMemcpyAsync(found, sc.oi.p, sizeof found, hipMemcpyDeviceToHost, s));
+  HIP_OK(hipMemcpyAsync(&nfound, sc.on.p, sizeof nfound, hipMemcpyDeviceToHost, s));
 
-  mark(3);
-  // ---- the padded adjacency of the touched nodes, the object ----------------
-  std::vector<uint32_t> dirty(nbr);
-  dirty.push_back(id);
-  std::sort(dirty.begin(), dirty.end());
-  dirty.erase(std::unique(dirty.begin(), dirty.end()), dirty.end());
-  std::vector<uint32_t> vals(dirty.size() * b.adj_stride, 0u);
-  for (size_t i = 0; i < dirty.size(); i++) {
-    const auto& node = b.graph[dirty[i]];
-    const size_t m = std::min<size_t>(node.size(), b.adj_stride);
-    for (size_t j = 0; j < m; j++) vals[i * b.adj_stride + j] = node[j].first;
+  // ---- the descent to the object's leaf (Tree.h:156-176) and the relink
+  //      chain of the neighbours, behind the search on the same stream: the
+  //      three need nothing from one another, so one wait serves them all ----
+  if (alloc_descent(sc.descent, 1)) return -1;
+  TreeSeedArgs t = tree_descent_args(ix, b, d_row, 1, sc.descent);
+  t.seed_size = 1;
+  t.k = 1;
+  t.all_leaf_nodes = 0;
+  HIP_OK(launch_tree_seeds(t, ix->metric, ix->otype, s));
+  uint32_t leaf = 0, cnt = 0;
+  HIP_OK(hipMemcpyAsync(&leaf, sc.descent.pleaf.p, sizeof leaf, hipMemcpyDeviceToHost, s));
+  HIP_OK(hipMemcpyAsync(&cnt, sc.descent.pcnt.p, sizeof cnt, hipMemcpyDeviceToHost, s));
+  std::vector<uint32_t> la(d ? d - 1 : 0), lb(d ? d - 1 : 0);
+  std::vector<float> ld(d ? d - 1 : 0);
+  if (relink(ix, sc, nbr.data(), d, la.data(), lb.data(), ld.data(), false)) return -1;
+  int serr = 0;
+  clk.mark(0);
+  if (take_device_error(ix, s, &serr)) return -1;
+  if (serr) return fail("ngt_amd_build_remove: device error flag %d in the duplicate search", serr);
+  if (nfound == 0) {
+    fail("Not found the specified id");
+    return 2;
   }
+  const uint32_t replace_id = nfound == 1 ? 0u : (found[0] == id ? found[1] : found[0]);
+  if (replace_id != 0) {
+    if (replace_id >= ix->nrows) return 2;
+    e = g.evaluated_edges_exist(ix->h_valid, replace_id, b.edge_size_for_search);
+    if (!e.empty()) return refuse(e);
+  }
+  clk.mark(1);
+
+  if (const int r = edit_leaf(b, id, replace_id, leaf, cnt)) return r;
+  clk.mark(2);
+
+  // ---- removeEdgesReliably on the host lists, the padded adjacency of the
+  //      touched nodes, the object ------------------------------------------------
+  std::vector<uint32_t> dirty;
+  g.apply_removal(id, nbr, nbr_d, la.data(), lb.data(), ld.data(), dirty);
+  clk.mark(3);
+  const std::vector<uint32_t> vals = g.adjacency_rows(dirty);
   HIP_OK(sc.dirty.upload_async(dirty.data(), dirty.size(), s));
   HIP_OK(sc.vals.upload_async(vals.data(), vals.size(), s));
-  HIP_OK(launch_adj_scatter(ix->adj.p, b.adj_stride, sc.dirty.p, sc.vals.p, (uint32_t)dirty.size(), s));
+  HIP_OK(launch_adj_scatter(ix->adj.p, g.adj_stride, sc.dirty.p, sc.vals.p, (uint32_t)dirty.size(), s));
   HIP_OK(hipStreamSynchronize(s));
   ix->adj_version++;
   b.longest_removed_list = std::max<uint64_t>(b.longest_removed_list, d);
-  mark(4);
+  clk.mark(4);
   return drop_object(ix, id);
 }
 
@@ -1007,17 +877,15 @@ extern "C" int ngt_amd_build_remove(ngt_amd_index* ix, const uint32_t* ids, uint
   ServeHold serve_hold(ix);
   BuildState& b = *ix->build;
   RemoveScratch& sc = b.remove_scratch;  // no allocation per id once warm
-  // NGT_AMD_BUILD_PROFILE=1: per-stage wall time on stderr
-  const bool prof = ngt_amd::knob("NGT_AMD_BUILD_PROFILE") != nullptr;
-  double st[5] = {0, 0, 0, 0, 0};
+  StageClock clk;  // no stream: the stages are timed as the host sees them
   for (uint64_t i = 0; i < n; i++) {
-    const int r = remove_one(ix, b, sc, ids[i], prof ? st : nullptr);
+    const int r = remove_one(ix, b, sc, ids[i], clk);
     if (r < 0) return -1;
     status[i] = (uint8_t)r;
   }
-  if (prof)
+  if (clk.on)
     fprintf(stderr, "build_remove %llu ids: enqueue %.3f s, wait %.3f s, leaf %.3f s, lists %.3f s, adjacency and "
-            "flag %.3f s\n", (unsigned long long)n, st[0], st[1], st[2], st[3], st[4]);
+            "flag %.3f s\n", (unsigned long long)n, clk.st[0], clk.st[1], clk.st[2], clk.st[3], clk.st[4]);
   return 0;
 }
 
@@ -1027,29 +895,40 @@ extern "C" uint64_t ngt_amd_build_longest_removed_list(const ngt_amd_index* ix) 
 
 extern "C" int ngt_amd_build_graph_size(const ngt_amd_index* ix, uint64_t* graph_size, uint64_t* nedges) {
   if (!ix || !ix->build || !graph_size || !nedges) return fail("ngt_amd_build_graph_size: bad arguments");
-  const BuildState& b = *ix->build;
-  *graph_size = b.graph_size;
-  uint64_t e = 0;
-  for (uint64_t v = 0; v < b.graph_size; v++) e += b.graph[v].size();
-  *nedges = e;
+  *graph_size = ix->build->g.graph_size;
+  *nedges = ix->build->g.edge_count();
   return 0;
 }
 
 extern "C" int ngt_amd_build_get_graph(const ngt_amd_index* ix, uint64_t* offsets, uint32_t* ids, float* dists) {
   if (!ix || !ix->build || !offsets) return fail("ngt_amd_build_get_graph: bad arguments");
-  const BuildState& b = *ix->build;
-  uint64_t e = 0;
-  offsets[0] = 0;
-  for (uint64_t v = 0; v < b.graph_size; v++) {
-    for (const auto& x : b.graph[v]) {
-      if (ids) ids[e] = x.first;
-      if (dists) dists[e] = x.second;
-      e++;
-    }
-    offsets[v + 1] = e;
-  }
+  ix->build->g.get_csr(offsets, ids, dists);
   return 0;
 }
+
+int ngt_amd::build_graph_to_host(const ngt_amd_index* ix, uint64_t nrows, std::vector<uint64_t>& off,
+                                 std::vector<uint32_t>& ids, std::vector<float>& dists) {
+  uint64_t gsize = 0, ne = 0;
+  if (ngt_amd_build_graph_size(ix, &gsize, &ne)) return -1;
+  std::vector<uint64_t> o(gsize + 1);
+  ids.resize(ne);
+  dists.resize(ne);
+  if (ngt_amd_build_get_graph(ix, o.data(), ids.data(), dists.data())) return -1;
+  off.assign(nrows + 1, ne);
+  for (uint64_t v = 0; v <= nrows && v <= gsize; v++) off[v] = o[v];
+  return 0;
+}
+
+void ngt_amd::build_mark_nodes(ngt_amd_index* ix, const std::vector<uint8_t>& node, uint64_t rows) {
+  for (uint64_t v = 0; v < rows; v++)
+    if (node[v]) ix->build->g.mark_node(v);
+}
+
+const std::vector<uint8_t>& ngt_amd::build_nodes(const ngt_amd_index* ix) { return ix->build->g.in_graph; }
+
+GlibcRandHost& ngt_amd::build_rand(ngt_amd_index* ix) { return ix->build->rnd; }
+
+uint32_t ngt_amd::build_root(const ngt_amd_index* ix) { return ix->build->root; }
 
 extern "C" int ngt_amd_build_tree_size(const ngt_amd_index* ix, uint32_t* n_leaf, uint32_t* n_internal,
                                        uint64_t* n_leaf_ids) {

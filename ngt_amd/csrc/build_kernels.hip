@@ -22,6 +22,7 @@
 #include "ngt_device.h"
 #include "ngt_kernels.h"
 #include "search_common.h"
+#include "stored_dispatch.h"
 
 namespace ngt_amd {
 
@@ -522,40 +523,6 @@ hipError_t launch_gather_rows(uint8_t* dst, const uint8_t* rows, uint64_t row_by
   return hipGetLastError();
 }
 
-#define NGT_BUILD_DISPATCH(METRIC, OTYPE, LAUNCH)                              \
-  do {                                                                         \
-    if ((OTYPE) == kFloat) {                                                   \
-      switch (METRIC) {                                                        \
-        case kL1: LAUNCH(kL1, float); break;                                   \
-        case kL2: LAUNCH(kL2, float); break;                                   \
-        case kAngle: LAUNCH(kAngle, float); break;                             \
-        case kCosine: LAUNCH(kCosine, float); break;                           \
-        case kNormalizedAngle: LAUNCH(kNormalizedAngle, float); break;         \
-        case kNormalizedCosine: LAUNCH(kNormalizedCosine, float); break;       \
-        case kNormalizedL2: LAUNCH(kNormalizedL2, float); break;               \
-        case kSparseJaccard: LAUNCH(kSparseJaccard, float); break;             \
-        case kPoincare: LAUNCH(kPoincare, float); break;                       \
-        case kLorentz: LAUNCH(kLorentz, float); break;                         \
-        default: return hipErrorInvalidValue;                                  \
-      }                                                                        \
-    } else if ((OTYPE) == kUint8) {                                            \
-      switch (METRIC) {                                                        \
-        case kL1: LAUNCH(kL1, uint8_t); break;                                 \
-        case kL2: LAUNCH(kL2, uint8_t); break;                                 \
-        case kHamming: LAUNCH(kHamming, uint8_t); break;                       \
-        case kJaccard: LAUNCH(kJaccard, uint8_t); break;                       \
-        case kAngle: LAUNCH(kAngle, uint8_t); break;                           \
-        case kCosine: LAUNCH(kCosine, uint8_t); break;                         \
-        case kNormalizedAngle: LAUNCH(kNormalizedAngle, uint8_t); break;       \
-        case kNormalizedCosine: LAUNCH(kNormalizedCosine, uint8_t); break;     \
-        case kNormalizedL2: LAUNCH(kNormalizedL2, uint8_t); break;             \
-        default: return hipErrorInvalidValue;                                  \
-      }                                                                        \
-    } else {                                                                   \
-      return hipErrorInvalidValue;                                             \
-    }                                                                          \
-  } while (0)
-
 hipError_t launch_tree_insert(const TreeBuildArgs& a, int metric, int otype, hipStream_t s) {
   if (a.n == 0) return hipSuccess;
   const uint32_t nf = a.leaf_size + 1;
@@ -563,7 +530,7 @@ hipError_t launch_tree_insert(const TreeBuildArgs& a, int metric, int otype, hip
                      (size_t)nf * nf * sizeof(float) + 2 * 256 * sizeof(uint32_t) + 4 * sizeof(uint32_t);
   if (lds > 64 * 1024 || a.repl_cap > 256) return hipErrorInvalidValue;
 #define L_TI(MM, TT) hipLaunchKernelGGL((ngt_tree_insert_kernel<MM, TT>), dim3(1), dim3(256), lds, s, a)
-  NGT_BUILD_DISPATCH(metric, otype, L_TI);
+  NGT_STORED_DISPATCH(metric, otype, L_TI);
 #undef L_TI
   return hipGetLastError();
 }
@@ -574,7 +541,7 @@ hipError_t launch_batch_pairs(const BatchPairArgs& a, int metric, int otype, hip
   uint64_t blocks = (np * 4 + 255) / 256;
   if (blocks > 16384) blocks = 16384;
 #define L_BP(MM, TT) hipLaunchKernelGGL((ngt_batch_pairs_kernel<MM, TT>), dim3((uint32_t)blocks), dim3(256), 0, s, a)
-  NGT_BUILD_DISPATCH(metric, otype, L_BP);
+  NGT_STORED_DISPATCH(metric, otype, L_BP);
 #undef L_BP
   return hipGetLastError();
 }

@@ -272,14 +272,7 @@ std::string append_object(CapiIndex* ix, const T* obj, uint32_t dim, uint32_t& i
 // slot flags, the pivots' presence and the root.
 std::string fetch_session(CapiIndex* ix, bool after_build) {
   HostIndex& h = ix->host;
-  uint64_t gsize = 0, ne = 0;
-  if (ngt_amd_build_graph_size(ix->dev, &gsize, &ne)) return amd_err();
-  std::vector<uint64_t> off(gsize + 1);
-  h.edges.resize(ne);
-  h.edge_dists.resize(ne);
-  if (ngt_amd_build_get_graph(ix->dev, off.data(), h.edges.data(), h.edge_dists.data())) return amd_err();
-  h.edge_off.assign(h.nrows + 1, ne);
-  for (uint64_t v = 0; v <= h.nrows && v <= gsize; v++) h.edge_off[v] = off[v];
+  if (ngt_amd::build_graph_to_host(ix->dev, h.nrows, h.edge_off, h.edges, h.edge_dists)) return amd_err();
   if (after_build) h.prevsize.assign(h.nrows, 0);
   ngt_amd::HostTree got;
   if (ngt_amd::build_tree_to_host(ix->dev, h.row_bytes, got)) return amd_err();

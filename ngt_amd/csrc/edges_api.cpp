@@ -109,32 +109,21 @@ struct Optimizer {
       cut_since_build = false;
     }
     if (ngt_amd_build_begin(ix, &bp)) return -1;
-    ix->build->rnd = rnd;  // the stream goes on where the query draw left it
+    build_rand(ix) = rnd;  // the stream goes on where the query draw left it
     if (have_prev) {
       if (ngt_amd_build_set_graph(ix, h.off.data(), h.ids.data(), h.d.data(), graph_rows)) return -1;
       // a node whose re-cut list came out empty is still a node: not inserted again
-      BuildState& b = *ix->build;
-      for (uint64_t v = 0; v < graph_rows; v++)
-        if (node[v]) {
-          b.in_graph[v] = 1;
-          b.graph_size = std::max<uint64_t>(b.graph_size, v + 1);
-        }
+      build_mark_nodes(ix, node, graph_rows);
       if (build_tree_from_host(ix, tree, (uint32_t)tree.in_parent.size(), tree.root)) return -1;
     }
     if (ngt_amd_build_insert(ix, 1, end_id)) return -1;
-    rnd = ix->build->rnd;
-    uint64_t gsize = 0, ne = 0;
-    if (ngt_amd_build_graph_size(ix, &gsize, &ne)) return -1;
-    std::vector<uint64_t> off(gsize + 1);
-    h.ids.resize(ne);
-    h.d.resize(ne);
-    if (ngt_amd_build_get_graph(ix, off.data(), h.ids.data(), h.d.data())) return -1;
-    h.off.assign((size_t)n + 1, ne);
-    for (uint64_t v = 0; v <= gsize && v <= n; v++) h.off[v] = off[v];
-    graph_rows = gsize;
-    node.assign(ix->build->in_graph.begin(), ix->build->in_graph.end());
+    rnd = build_rand(ix);
+    uint64_t ne = 0;
+    if (ngt_amd_build_graph_size(ix, &graph_rows, &ne)) return -1;
+    if (build_graph_to_host(ix, n, h.off, h.ids, h.d)) return -1;
+    node = build_nodes(ix);
     if (build_tree_to_host(ix, ix->row_bytes, tree)) return -1;
-    tree.root = ix->build->root;
+    tree.root = build_root(ix);
     have_prev = true;
     // the pseudo ground truth searches the sample's whole graph
     if (ngt_amd_index_set_graph(ix, h.off.data(), h.ids.data(), ne)) return -1;

@@ -14,6 +14,7 @@
 #include "../../include/ngt_amd.h"
 #include "ngt_kernels.h"
 #include "search_plan.h"
+#include "session_graph.h"
 
 namespace ngt_amd {
 
@@ -198,53 +199,29 @@ struct CallCtx {
   }
 };
 
-// glibc random(3) TYPE_3 (random_r), host side: the rand() stream of a fresh
-// process (srand(1)), for getRandomSeeds during construction.
-struct GlibcRandHost {
-  uint32_t s[31];
-  int f = 3, r = 0;
-  void seed(uint32_t sd) {
-    int32_t word = (int32_t)(sd == 0 ? 1u : sd);
-    s[0] = (uint32_t)word;
-    for (int i = 1; i < 31; i++) {
-      int32_t hi = word / 127773, lo = word % 127773;
-      word = 16807 * lo - 2836 * hi;
-      if (word < 0) word += 2147483647;
-      s[i] = (uint32_t)word;
-    }
-    f = 3;
-    r = 0;
-    for (int i = 0; i < 310; i++) next();
-  }
-  int next() {
-    s[f] += s[r];
-    int res = (int)((s[f] >> 1) & 0x7fffffff);
-    f = f == 30 ? 0 : f + 1;
-    r = r == 30 ? 0 : r + 1;
-    return res;
-  }
-};
-
 // ANNG construction state (build.cpp): the graph being built (host, sorted
 // edge lists), the DVP tree being built (HBM, fixed-capacity node arrays) and
 // the padded search adjacency the insertion searches read (HBM).
 struct Server;  // serve.cpp
 
+// the buffers a descent of nq queries over the session's tree writes (build.cpp)
+struct DescentBufs {
+  DevBuf<uint32_t> tseeds, tcnt, pleaf, pcnt;
+  DevBuf<float> pdist;
+};
+
 // device scratch of object removal (build.cpp), kept for the session
 struct RemoveScratch {
-  DevBuf<uint32_t> ids, la, lb, seed, oi, on, tseeds, tcnt, pleaf, pcnt, dirty, vals;
+  DevBuf<uint32_t> ids, la, lb, seed, oi, on, dirty, vals;
   DevBuf<uint64_t> soff;
-  DevBuf<float> ld, od, pdist, matrix;
+  DevBuf<float> ld, od, matrix;
+  DescentBufs descent;
 };
 
 struct BuildState {
-  int32_t edge_size_for_creation = 10, edge_size_for_search = 40, batch_size = 200, seed_size = 10;
+  int32_t edge_size_for_search = 40, batch_size = 200, seed_size = 10;
   float epsilon_for_creation = 0.1f;
-  int32_t graph_type = NGT_AMD_GRAPH_ANNG;         // the insertion rule (build.cpp)
-  int32_t outgoing_edge = 10, incoming_edge = 80;  // ONNG at insertion (Graph.h:637-655)
-  std::vector<std::vector<std::pair<uint32_t, float>>> graph;  // graph repository, slot = object id
-  std::vector<uint8_t> in_graph;
-  uint64_t graph_size = 0;       // GraphRepository::size() (max inserted id + 1, 0 when empty)
+  SessionGraph g;  // the graph repository and its rules (session_graph.h)
   // tree (leaf ids and internal ids start at 1; leaf 1 is the initial root)
   DevBuf<uint32_t> lf_parent, lf_count, lf_ids, in_parent, in_child, counts;
   DevBuf<uint8_t> lf_has_pivot, lf_pivot, in_pivot;
@@ -253,12 +230,7 @@ struct BuildState {
   uint32_t n_leaf = 2, n_internal = 1;  // next ids
   uint32_t root = 0x80000001u;
   GlibcRandHost rnd;
-  uint64_t adj_stride = 0;
-  // removal (ngt_amd_build_remove): the graph repository slots loaded by
-  // ngt_amd_build_set_graph -- a valid object below it has a node even with
-  // no edges left -- and the longest neighbour list a removal relinked
-  uint64_t node_rows = 0;
-  uint64_t longest_removed_list = 0;
+  uint64_t longest_removed_list = 0;  // the longest neighbour list a removal relinked
   RemoveScratch remove_scratch;
 };
 
@@ -410,5 +382,16 @@ ngt_amd_search_params library_search_params(uint64_t nrows, uint32_t k, float ep
 struct HostTree;
 int build_tree_to_host(const ngt_amd_index* ix, uint64_t row_bytes, HostTree& t);
 int build_tree_from_host(ngt_amd_index* ix, const HostTree& t, uint32_t n_internal, uint32_t root);
+// A build session's graph as CSR over nrows slots: off [nrows + 1], the slots
+// past the graph's size empty.
+int build_graph_to_host(const ngt_amd_index* ix, uint64_t nrows, std::vector<uint64_t>& off,
+                        std::vector<uint32_t>& ids, std::vector<float>& dists);
+// What a caller that carries a session's state from one ngt_amd_build_begin to
+// the next reads and sets: the slots that are nodes (a node may have no edge:
+// construction does not insert it again), the rand() stream, the tree's root.
+const std::vector<uint8_t>& build_nodes(const ngt_amd_index* ix);
+void build_mark_nodes(ngt_amd_index* ix, const std::vector<uint8_t>& node, uint64_t rows);
+GlibcRandHost& build_rand(ngt_amd_index* ix);
+uint32_t build_root(const ngt_amd_index* ix);
 
 }  // namespace ngt_amd

@@ -23,6 +23,7 @@
 #include "index_internal.h"
 #include "ngt_kernels.h"
 #include "prep_kernels.h"
+#include "session_graph.h"
 
 using namespace ngt_amd;
 
@@ -702,7 +703,7 @@ static int run_search(ngt_amd_index* ix, SearchCtx* c, const ngt_amd_search_para
 // process-wide glibc rand(), so a fresh `ngt search -i g` process draws from
 // seed 1.  The GPU runtime in this process may call rand() itself, which
 // would shift that stream between searches; the library therefore keeps its
-// own glibc TYPE_3 generator (random_r restated, index_internal.h), seeded 1
+// own glibc TYPE_3 generator (random_r restated, session_graph.h), seeded 1
 // like a fresh process and reseeded only by ngt_amd_srand -- the reference's
 // sequence, independent of anything else in the process.
 static std::mutex g_rand_mu;
@@ -723,20 +724,8 @@ extern "C" void ngt_amd_srand(unsigned int seed) {
 // One GraphIndex::getRandomSeeds (Index.h:775-801) appended to `seeds`; the
 // caller holds g_rand_mu.
 static void draw_random_seeds(ngt_amd_index* ix, GlibcRandHost& rnd, std::vector<uint32_t>& seeds) {
-  const size_t start = seeds.size();
-  const size_t repo = ix->nrows == 0 ? 0 : ix->nrows - 1;
-  const size_t ss = std::min<size_t>(repo, (size_t)std::max(ix->seed_size, 0));
-  size_t empty = 0;
-  while (seeds.size() - start < ss) {
-    double random = ((double)rnd.next() + 1.0) / ((double)RAND_MAX + 2.0);
-    size_t idx = (size_t)floor((double)repo * random) + 1;
-    if (ix->h_graph_empty[idx]) {
-      if (++empty > repo) break;
-      continue;
-    }
-    if (std::find(seeds.begin() + start, seeds.end(), (uint32_t)idx) != seeds.end()) continue;
-    seeds.push_back((uint32_t)idx);
-  }
+  get_random_seeds(rnd, ix->nrows == 0 ? 0 : ix->nrows - 1, (size_t)std::max(ix->seed_size, 0),
+                   [&](size_t idx) { return ix->h_graph_empty[idx] != 0; }, seeds);
 }
 
 std::vector<uint32_t> ngt_amd::random_seed_lists(ngt_amd_index* ix, uint32_t nq, std::vector<uint64_t>& off) {

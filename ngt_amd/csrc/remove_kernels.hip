@@ -26,6 +26,7 @@
 #include "ngt_kernels.h"
 #include "remove_kernels.h"
 #include "search_common.h"
+#include "stored_dispatch.h"
 
 namespace ngt_amd {
 namespace removal {
@@ -119,40 +120,6 @@ __global__ void __launch_bounds__(kMatrixChainThreads) ngt_relink_chain_kernel(R
   }
 }
 
-#define NGT_REMOVE_DISPATCH(METRIC, OTYPE, LAUNCH)                             \
-  do {                                                                         \
-    if ((OTYPE) == kFloat) {                                                   \
-      switch (METRIC) {                                                        \
-        case kL1: LAUNCH(kL1, float); break;                                   \
-        case kL2: LAUNCH(kL2, float); break;                                   \
-        case kAngle: LAUNCH(kAngle, float); break;                             \
-        case kCosine: LAUNCH(kCosine, float); break;                           \
-        case kNormalizedAngle: LAUNCH(kNormalizedAngle, float); break;         \
-        case kNormalizedCosine: LAUNCH(kNormalizedCosine, float); break;       \
-        case kNormalizedL2: LAUNCH(kNormalizedL2, float); break;               \
-        case kSparseJaccard: LAUNCH(kSparseJaccard, float); break;             \
-        case kPoincare: LAUNCH(kPoincare, float); break;                       \
-        case kLorentz: LAUNCH(kLorentz, float); break;                         \
-        default: return hipErrorInvalidValue;                                  \
-      }                                                                        \
-    } else if ((OTYPE) == kUint8) {                                            \
-      switch (METRIC) {                                                        \
-        case kL1: LAUNCH(kL1, uint8_t); break;                                 \
-        case kL2: LAUNCH(kL2, uint8_t); break;                                 \
-        case kHamming: LAUNCH(kHamming, uint8_t); break;                       \
-        case kJaccard: LAUNCH(kJaccard, uint8_t); break;                       \
-        case kAngle: LAUNCH(kAngle, uint8_t); break;                           \
-        case kCosine: LAUNCH(kCosine, uint8_t); break;                         \
-        case kNormalizedAngle: LAUNCH(kNormalizedAngle, uint8_t); break;       \
-        case kNormalizedCosine: LAUNCH(kNormalizedCosine, uint8_t); break;     \
-        case kNormalizedL2: LAUNCH(kNormalizedL2, uint8_t); break;             \
-        default: return hipErrorInvalidValue;                                  \
-      }                                                                        \
-    } else {                                                                   \
-      return hipErrorInvalidValue;                                             \
-    }                                                                          \
-  } while (0)
-
 }  // namespace
 
 size_t fast_lds_bytes(uint32_t d, uint64_t row_bytes, uint32_t cap) {
@@ -167,7 +134,7 @@ hipError_t launch_relink_fast(const RelinkArgs& a, int metric, int otype, hipStr
   if (lds == 0) return hipErrorInvalidValue;
 #define L_RF(MM, TT) \
   hipLaunchKernelGGL((ngt_relink_fast_kernel<MM, TT>), dim3(1), dim3(kChainThreads), lds, s, a)
-  NGT_REMOVE_DISPATCH(metric, otype, L_RF);
+  NGT_STORED_DISPATCH(metric, otype, L_RF);
 #undef L_RF
   return hipGetLastError();
 }
@@ -179,7 +146,7 @@ hipError_t launch_relink_matrix(const RelinkArgs& a, int metric, int otype, hipS
   if (blocks > 16384) blocks = 16384;
 #define L_RM(MM, TT) \
   hipLaunchKernelGGL((ngt_relink_matrix_kernel<MM, TT>), dim3((uint32_t)blocks), dim3(256), 0, s, a)
-  NGT_REMOVE_DISPATCH(metric, otype, L_RM);
+  NGT_STORED_DISPATCH(metric, otype, L_RM);
 #undef L_RM
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
