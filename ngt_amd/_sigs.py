@@ -127,6 +127,7 @@ def declare(L):
         "ngt_amd_stream_error_word": (c_int, [vp, vp, vp]),
         "ngt_amd_last_search_budget": (c_uint32, [vp]),
         "ngt_amd_last_search_filtered": (c_int, [vp]),
+        "ngt_amd_last_scan_kernel": (c_int, [vp]),
         "ngt_amd_build_begin": (c_int, [vp, POINTER(BuildParams)]),
         "ngt_amd_build_set_onng_edges": (c_int, [vp, c_int32, c_int32]),
         "ngt_amd_build_insert": (c_int, [vp, c_uint64, c_uint64]),

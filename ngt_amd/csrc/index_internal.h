@@ -254,7 +254,10 @@ struct ngt_amd_index {
     DevBuf<uint32_t> xmax;
     uint64_t version = ~0ull;
     int passes = 0;
+    DevBuf<int32_t> u8_nx;       // uint8 L2 scan (scan_u8.hip): the rows' norm column
+    uint64_t u8_version = ~0ull;
   } scan;
+  std::atomic<int> last_scan{0};  // the kernel of the latest exact scan (ngt_amd_last_scan_kernel)
   struct {                       // 1-byte filter copy of L2 float rows (filter_kernels.hip)
     DevBuf<uint8_t> codes;
     DevBuf<uint32_t> st;

@@ -23,6 +23,7 @@
 #include "index_internal.h"
 #include "ngt_kernels.h"
 #include "prep_kernels.h"
+#include "scan_u8_bound.h"
 #include "session_graph.h"
 
 using namespace ngt_amd;
@@ -1137,6 +1138,63 @@ static int linear_search_mfma(ngt_amd_index* ix, SearchCtx* c, LinearArgs& a, hi
   return 0;
 }
 
+// The rows' norm column of the uint8 L2 scan (scan_u8.hip), built once per
+// version of the rows.
+static int ensure_scan_u8_rows(ngt_amd_index* ix, hipStream_t s) {
+  std::lock_guard<std::mutex> lk(ix->mu);
+  if (ix->scan.u8_version == ix->rows_version) return 0;
+  const uint64_t npad = (ix->nrows + 255) / 256 * 256;  // 256-row scan tiles
+  HIP_OK(ix->scan.u8_nx.alloc(npad));
+  HIP_OK(launch_scan_u8_norms(ix->rows.p, ix->row_bytes, ix->nrows, ix->valid.p, (int)ix->dp, ix->scan.u8_nx.p, npad,
+                              s));
+  // other streams may scan as soon as the version is published
+  HIP_OK(hipStreamSynchronize(s));
+  ix->scan.u8_version = ix->rows_version;
+  return 0;
+}
+
+// uint8 L2 batches: exact integer sums from the int8 matrix cores
+// (scan_u8.hip), per-part lists merged like every other scan's.
+static int linear_search_u8(ngt_amd_index* ix, SearchCtx* c, LinearArgs& a, hipStream_t s) {
+  if (ensure_scan_u8_rows(ix, s)) return -1;
+  const uint32_t mblocks = (a.nq + 127) / 128;  // 128 queries per workgroup
+  const uint32_t ntiles = (uint32_t)((ix->nrows + 255) / 256);
+  // one workgroup per CU: every query block x floor(CUs / blocks) parts
+  uint32_t np = std::max<uint32_t>(1, (uint32_t)ix->cu_count / mblocks);
+  np = std::min(np, ntiles);
+  const uint32_t per = (ntiles + np - 1) / np;
+  U8ScanArgs m{};
+  m.rows = ix->rows.p;
+  m.row_bytes = ix->row_bytes;
+  m.nrows = ix->nrows;
+  m.nx = ix->scan.u8_nx.p;
+  m.queries = a.queries;
+  m.query_bytes = a.query_bytes;
+  m.nq = a.nq;
+  m.k = a.k;
+  m.dp = (int)ix->dp;
+  m.pend = scan_u8_lds_bytes(a.k, m.dp, 16) <= 160 * 1024 ? 16 : 8;
+  m.mblocks = mblocks;
+  m.ntiles = ntiles;
+  m.tiles_per_part = per;
+  m.nparts = (ntiles + per - 1) / per;
+  m.radius = a.radius;
+  m.s_init = kU8SumAll;
+  if (a.radius >= 0.0 && a.radius < 16384.0) {
+    float d = (float)a.radius;  // rounded up: the exact test is the kernel's
+    if ((double)d < a.radius) d = u8_next_up(d);
+    m.s_init = u8_sum_threshold(d);
+  }
+  HIP_OK(c->partial.alloc((size_t)a.nq * m.nparts * a.k));
+  m.partial = c->partial.p;
+  HIP_OK(launch_scan_u8(m, s));
+  a.partial = m.partial;
+  HIP_OK(launch_linear_merge(a, m.nparts, s));
+  return 0;
+}
+
+extern "C" int ngt_amd_last_scan_kernel(const ngt_amd_index* ix) { return ix ? ix->last_scan.load() : 0; }
+
 extern "C" int ngt_amd_linear_search_device(ngt_amd_index* ix, const void* d_queries, uint64_t query_bytes,
                                             uint32_t nq, uint32_t k, double radius, uint32_t* d_ids,
                                             float* d_dists, uint32_t* d_n, void* stream) {
@@ -1175,8 +1233,20 @@ extern "C" int ngt_amd_linear_search_device(ngt_amd_index* ix, const void* d_que
     return !(v && atoi(v) == 0);
   }();
   if (use_mfma && nq >= 32 && ix->otype == NGT_AMD_OBJECT_FLOAT && k <= 16 &&
-      (ix->metric == NGT_AMD_DISTANCE_L2 || ix->metric == NGT_AMD_DISTANCE_COSINE))
+      (ix->metric == NGT_AMD_DISTANCE_L2 || ix->metric == NGT_AMD_DISTANCE_COSINE)) {
+    ix->last_scan = 2;
     return linear_search_mfma(ix, c, a, s);
+  }
+  // Batches of queries, uint8 L2: exact integer sums on the int8 matrix
+  // cores (scan_u8.hip); k <= 16 is the length of its LDS lists.  The knob is
+  // read per call, so one process can compare both paths.
+  const char* u8_knob = ngt_amd::knob("NGT_AMD_LINEAR_U8");
+  if (!(u8_knob && atoi(u8_knob) == 0) && nq >= 32 && ix->otype == NGT_AMD_OBJECT_UINT8 &&
+      ix->metric == NGT_AMD_DISTANCE_L2 && k <= 16 && ix->dp <= 1024 && ix->dp % 16 == 0 && query_bytes % 16 == 0 &&
+      (uintptr_t)d_queries % 16 == 0 && ix->row_bytes % 16 == 0) {
+    ix->last_scan = 3;
+    return linear_search_u8(ix, c, a, s);
+  }
   // Batches of queries: the query-tiled scan (128 queries per workgroup,
   // packed FMA, scan_kernels.hip) over enough row parts for ~3 workgroups
   // per CU slot; small batches keep the quad-per-row kernel below.
@@ -1196,6 +1266,7 @@ extern "C" int ngt_amd_linear_search_device(ngt_amd_index* ix, const void* d_que
     hipError_t e = launch_linear_scan(a, ix->metric, ix->otype, (uint32_t)nparts, (uint32_t)per, s);
     if (e == hipSuccess) {
       HIP_OK(launch_linear_merge(a, (uint32_t)nparts, s));
+      ix->last_scan = 1;
       return 0;
     }
     if (e != hipErrorNotSupported) return fail("ngt_amd_linear_search_device: scan launch failed: %s",
@@ -1215,6 +1286,7 @@ extern "C" int ngt_amd_linear_search_device(ngt_amd_index* ix, const void* d_que
   HIP_OK(c->partial.alloc((size_t)nq * nslices * k));
   a.partial = c->partial.p;
   HIP_OK(launch_linear_search(a, ix->metric, ix->otype, nslices, s));
+  ix->last_scan = 0;
   return 0;
 }
 

@@ -406,6 +406,28 @@ hipError_t launch_scan_prep(const ScanPrepArgs& a, bool cosine, bool query, hipS
 hipError_t launch_scan_mfma(const MfmaScanArgs& a, int metric, int passes, hipStream_t s);
 size_t scan_mfma_lds_bytes(uint32_t k);
 
+// uint8 L2 exact scan on the int8 matrix cores (scan_u8.hip): Dp <= 1024 a
+// multiple of 16, k <= 16, query rows 16-byte aligned.
+struct U8ScanArgs {
+  const uint8_t* rows;
+  uint64_t row_bytes;
+  uint64_t nrows;
+  const int32_t* nx;             // [ntiles * 256] |x - 128|^2, kU8SumNever for removed / padding rows
+  const uint8_t* queries;
+  uint64_t query_bytes;
+  uint32_t nq, k;
+  int dp;
+  uint32_t pend;                 // pending slots per query (16; 8 where the LDS is short)
+  uint32_t mblocks, ntiles, tiles_per_part, nparts;
+  double radius;
+  int32_t s_init;                // the threshold of the radius, kU8SumAll without one
+  uint64_t* partial;             // [nq][nparts][k]
+};
+hipError_t launch_scan_u8_norms(const uint8_t* rows, uint64_t row_bytes, uint64_t nrows, const uint8_t* valid, int dp,
+                                int32_t* nx, uint64_t npad, hipStream_t s);
+hipError_t launch_scan_u8(const U8ScanArgs& a, hipStream_t s);
+size_t scan_u8_lds_bytes(uint32_t k, int dp, uint32_t pend);
+
 // ---- NGTQG (qg_kernels.hip) ------------------------------------------------
 struct QgLutArgs {
   const uint8_t* queries;        // prepared float query rows (padded dp)

@@ -214,6 +214,11 @@ class DeviceIndex(object):
         [6]: exact neighbour distances, [7]: seed distances)."""
         return bool(self.L.ngt_amd_last_search_filtered(self.h))
 
+    def last_scan_kernel(self):
+        """Kernel of the latest linear search on the index: 0 quad-per-row,
+        1 tiled FMA, 2 bf16 matrix-core filter, 3 uint8 L2 on the int8 matrix cores."""
+        return int(self.L.ngt_amd_last_scan_kernel(self.h))
+
     def last_search_lookahead(self):
         """Form of the latest graph-search launch: -1 one expansion per pop,
         0 lookahead with a wave per query, 1 lookahead with eight waves per query."""
