@@ -158,6 +158,7 @@ struct SearchCtx {
   DevBuf<uint16_t> sqh, sql;     // matrix-core scan: queries in fragment order
   DevBuf<float> shb;             // matrix-core scan: per-query filter base
   DevBuf<uint64_t> gthr;         // matrix-core scan: per-query k-th key shared by the parts
+  DevBuf<uint32_t> bq;           // uint8 L1 / Hamming scan: zero-padded queries
   DevBuf<uint32_t> ivf_cid, ivf_cn;  // NGTQ: global-codebook search results [nq][cbs], [nq]
   DevBuf<float> ivf_cd;
   DevBuf<int> err;               // device error flag of the launches on this stream

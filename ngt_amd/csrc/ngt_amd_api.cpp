@@ -1193,6 +1193,50 @@ static int linear_search_u8(ngt_amd_index* ix, SearchCtx* c, LinearArgs& a, hipS
   return 0;
 }
 
+// uint8 L1 / Hamming batches: a wave per 128 queries x one part of the rows,
+// lane = row, exact integer sums by v_sad_u8 / v_bcnt (scan_bytes.hip).
+static int linear_search_bytes(ngt_amd_index* ix, SearchCtx* c, LinearArgs& a, hipStream_t s) {
+  const uint32_t mblocks = (a.nq + 127) / 128;  // 128 queries per wave
+  const uint32_t ntiles = (uint32_t)((ix->nrows + 63) / 64);
+  // One resident set of waves over every query block: up to four waves per
+  // SIMD (they hide each other's scalar loads), three where a 256-byte row
+  // takes 144 VGPRs, fewer where the k-lists (128 k 8 bytes a wave) fill the
+  // CU's LDS first
+  uint32_t wpc = std::min<uint32_t>(ix->dp > 128 ? 12 : 16, (uint32_t)(ix->lds_per_cu / (128 * a.k * 8)));
+  wpc = std::max<uint32_t>(4, wpc / 4 * 4);
+  uint32_t np = std::max<uint32_t>(1, (uint32_t)ix->cu_count * wpc / mblocks);
+  np = std::min(np, ntiles);
+  const uint32_t per = (ntiles + np - 1) / np;
+  BytesScanArgs m{};
+  m.rows = ix->rows.p;
+  m.row_bytes = ix->row_bytes;
+  m.nrows = ix->nrows;
+  m.valid = ix->valid.p;
+  m.nq = a.nq;
+  m.k = a.k;
+  m.dp = (int)ix->dp;
+  m.mblocks = mblocks;
+  m.ntiles = ntiles;
+  m.tiles_per_part = per;
+  m.nparts = (ntiles + per - 1) / per;
+  // (radius < 0 || (double)d <= radius) of the quad kernel on d = (float)S:
+  // S <= floor(radius), as a bound on the keys (S << 32 | id)
+  m.key_init = ~0ull;
+  if (!(a.radius < 0.0)) {
+    if (!(a.radius >= 0.0)) m.key_init = 0;  // NaN: no distance passes
+    else if (a.radius < 4.0e9) m.key_init = ((uint64_t)a.radius + 1) << 32;
+  }
+  HIP_OK(c->bq.alloc((size_t)mblocks * 128 * scan_bytes_chunks(m.dp) * 4));
+  HIP_OK(launch_scan_bytes_prep(a.queries, a.query_bytes, a.nq, m.dp, c->bq.p, mblocks, s));
+  m.qpad = c->bq.p;
+  HIP_OK(c->partial.alloc((size_t)a.nq * m.nparts * a.k));
+  m.partial = c->partial.p;
+  HIP_OK(launch_scan_bytes(m, ix->metric, s));
+  a.partial = m.partial;
+  HIP_OK(launch_linear_merge(a, m.nparts, s));
+  return 0;
+}
+
 extern "C" int ngt_amd_last_scan_kernel(const ngt_amd_index* ix) { return ix ? ix->last_scan.load() : 0; }
 
 extern "C" int ngt_amd_linear_search_device(ngt_amd_index* ix, const void* d_queries, uint64_t query_bytes,
@@ -1246,6 +1290,18 @@ extern "C" int ngt_amd_linear_search_device(ngt_amd_index* ix, const void* d_que
       (uintptr_t)d_queries % 16 == 0 && ix->row_bytes % 16 == 0) {
     ix->last_scan = 3;
     return linear_search_u8(ix, c, a, s);
+  }
+  // Batches of queries, uint8 L1 / Hamming: exact integer sums by packed
+  // byte-SAD and popcount (scan_bytes.hip); k <= 16 is the length of its LDS
+  // lists, Dp <= 256 the row a lane keeps in registers twice over.  Rows are
+  // read 16 bytes, queries 4 bytes at a time.  The knob is read per call.
+  const char* bytes_knob = ngt_amd::knob("NGT_AMD_LINEAR_BYTES");
+  if (!(bytes_knob && atoi(bytes_knob) == 0) && nq >= 32 && ix->otype == NGT_AMD_OBJECT_UINT8 &&
+      (ix->metric == NGT_AMD_DISTANCE_L1 || ix->metric == NGT_AMD_DISTANCE_HAMMING) && k <= 16 && ix->dp <= 256 &&
+      ix->dp % 16 == 0 && ix->row_bytes % 16 == 0 && query_bytes % 4 == 0 && (uintptr_t)d_queries % 4 == 0 &&
+      ix->nrows > 1) {
+    ix->last_scan = 4;
+    return linear_search_bytes(ix, c, a, s);
   }
   // Batches of queries: the query-tiled scan (128 queries per workgroup,
   // packed FMA, scan_kernels.hip) over enough row parts for ~3 workgroups

@@ -428,6 +428,25 @@ hipError_t launch_scan_u8_norms(const uint8_t* rows, uint64_t row_bytes, uint64_
 hipError_t launch_scan_u8(const U8ScanArgs& a, hipStream_t s);
 size_t scan_u8_lds_bytes(uint32_t k, int dp, uint32_t pend);
 
+// uint8 L1 / Hamming exact scan on packed byte-SAD and popcount
+// (scan_bytes.hip): Dp <= 256 a multiple of 16, k <= 16, rows 16-byte aligned.
+struct BytesScanArgs {
+  const uint8_t* rows;
+  uint64_t row_bytes;
+  uint64_t nrows;                // > 1
+  const uint8_t* valid;          // [nrows] or null
+  const uint32_t* qpad;          // [mblocks * 128][4 * scan_bytes_chunks(dp)] zero-padded queries, read-only
+  uint32_t nq, k;
+  int dp;
+  uint32_t mblocks, ntiles, tiles_per_part, nparts;  // 64-row tiles
+  uint64_t key_init;             // the radius as a (S << 32 | id) bound, ~0 without one
+  uint64_t* partial;             // [nq][nparts][k]
+};
+int scan_bytes_chunks(int dp);   // 16-byte chunks of a row in registers: 1, 2, 4, 8 or 16
+hipError_t launch_scan_bytes_prep(const uint8_t* queries, uint64_t query_bytes, uint32_t nq, int dp, uint32_t* qpad,
+                                  uint32_t mblocks, hipStream_t s);
+hipError_t launch_scan_bytes(const BytesScanArgs& a, int metric, hipStream_t s);
+
 // ---- NGTQG (qg_kernels.hip) ------------------------------------------------
 struct QgLutArgs {
   const uint8_t* queries;        // prepared float query rows (padded dp)

@@ -216,7 +216,8 @@ class DeviceIndex(object):
 
     def last_scan_kernel(self):
         """Kernel of the latest linear search on the index: 0 quad-per-row,
-        1 tiled FMA, 2 bf16 matrix-core filter, 3 uint8 L2 on the int8 matrix cores."""
+        1 tiled FMA, 2 bf16 matrix-core filter, 3 uint8 L2 on the int8 matrix cores,
+        4 uint8 L1 / Hamming on packed byte-SAD and popcount."""
         return int(self.L.ngt_amd_last_scan_kernel(self.h))
 
     def last_search_lookahead(self):
