@@ -1007,7 +1007,9 @@ static int ensure_scan_rows(ngt_amd_index* ix, int passes, hipStream_t s) {
   return 0;
 }
 
-static int linear_search_mfma(ngt_amd_index* ix, SearchCtx* c, LinearArgs& a, hipStream_t s) {
+// wide: lists of 17 .. 128 results (scan_mfma_wide.hip) -- the same operands,
+// bounds, parts and merge; the kernel sorts its lists in place in `partial`.
+static int linear_search_mfma(ngt_amd_index* ix, SearchCtx* c, LinearArgs& a, hipStream_t s, bool wide = false) {
   const int passes = scan_passes();
   if (ensure_scan_rows(ix, passes, s)) return -1;
   const bool cosine = ix->metric == NGT_AMD_DISTANCE_COSINE;
@@ -1039,15 +1041,22 @@ static int linear_search_mfma(ngt_amd_index* ix, SearchCtx* c, LinearArgs& a, hi
   p.kappa_boot = (float)(cosine ? 2.0 * kappa : kappa + rho);
   HIP_OK(launch_scan_prep(p, cosine, true, s));
 
-  // Launches of at most one workgroup per CU.  Default: one launch, every
-  // query block x floor(CUs / blocks) parts (a workgroup keeps its queries'
-  // k-lists for its whole part; each part costs ~k ln(rows / k) candidates per
-  // query, so few long parts).
+  // One launch: every query block x floor(CUs / blocks) parts, at least one
+  // and no more than the tiles (or the wide scan's test cap) -- one workgroup
+  // per CU at most while the query blocks are no more than the CUs (a
+  // workgroup keeps its queries' k-lists for its whole part; each part costs
+  // ~k ln(rows / k) candidates per query, so few long parts).
   const uint32_t ntiles = (uint32_t)((ix->nrows + 255) / 256);
   const uint32_t per_launch = mblocks;
+  // wide only, for tests: at most this many parts, so that a small table
+  // still has parts of several tiles
+  uint32_t parts_cap = UINT32_MAX;
+  if (wide)
+    if (const char* v = ngt_amd::knob("NGT_AMD_SCAN_WIDE_PARTS"))
+      if (atoi(v) > 0) parts_cap = (uint32_t)atoi(v);
   auto parts_of = [&](uint32_t mbc) -> uint32_t {
     uint32_t np = std::max<uint32_t>(1, (uint32_t)ix->cu_count / mbc);
-    np = std::min(np, ntiles);
+    np = std::min(std::min(np, ntiles), parts_cap);
     const uint32_t per = (ntiles + np - 1) / np;
     return (ntiles + per - 1) / per;
   };
@@ -1118,7 +1127,7 @@ static int linear_search_mfma(ngt_amd_index* ix, SearchCtx* c, LinearArgs& a, hi
     m.nparts = nparts;
     m.tiles_per_part = (ntiles + nparts - 1) / nparts;
     m.partial = c->partial.p + poff;
-    HIP_OK(launch_scan_mfma(m, ix->metric, passes, s));
+    HIP_OK(wide ? launch_scan_mfma_wide(m, ix->metric, passes, s) : launch_scan_mfma(m, ix->metric, passes, s));
     LinearArgs ac = a;
     ac.nq = nqc;
     ac.partial = m.partial;
@@ -1132,8 +1141,8 @@ static int linear_search_mfma(ngt_amd_index* ix, SearchCtx* c, LinearArgs& a, hi
     unsigned long long h[4];
     HIP_OK(hipMemcpyAsync(h, d_stats.p, sizeof(h), hipMemcpyDeviceToHost, s));
     HIP_OK(hipStreamSynchronize(s));
-    fprintf(stderr, "scan_mfma: nq %u launches %u candidates %llu rounds %llu process_requests %llu\n", a.nq,
-            (mblocks + per_launch - 1) / per_launch, h[0], h[1], h[2]);
+    fprintf(stderr, "scan_mfma%s: nq %u launches %u candidates %llu rounds %llu process_requests %llu\n",
+            wide ? "_wide" : "", a.nq, (mblocks + per_launch - 1) / per_launch, h[0], h[1], h[2]);
   }
   return 0;
 }
@@ -1280,6 +1289,15 @@ extern "C" int ngt_amd_linear_search_device(ngt_amd_index* ix, const void* d_que
       (ix->metric == NGT_AMD_DISTANCE_L2 || ix->metric == NGT_AMD_DISTANCE_COSINE)) {
     ix->last_scan = 2;
     return linear_search_mfma(ix, c, a, s);
+  }
+  // The same filter with lists of 17 .. 128 results (scan_mfma_wide.hip): the
+  // lists are sorted in place in the partial buffer by wave-cooperative
+  // rounds, so the LDS does not grow with k.  The knob is read per call.
+  const char* wide_knob = ngt_amd::knob("NGT_AMD_LINEAR_WIDE");
+  if (use_mfma && !(wide_knob && atoi(wide_knob) == 0) && nq >= 32 && ix->otype == NGT_AMD_OBJECT_FLOAT && k >= 17 &&
+      k <= 128 && (ix->metric == NGT_AMD_DISTANCE_L2 || ix->metric == NGT_AMD_DISTANCE_COSINE)) {
+    ix->last_scan = 5;
+    return linear_search_mfma(ix, c, a, s, true);
   }
   // Batches of queries, uint8 L2: exact integer sums on the int8 matrix
   // cores (scan_u8.hip); k <= 16 is the length of its LDS lists.  The knob is

@@ -397,7 +397,8 @@ struct MfmaScanArgs {
   uint32_t xcd;                  // parts a multiple of 8, part p on XCD p % 8
   double radius;
   float scale, t_init;
-  uint32_t dbg;                  // profiling knobs (NGT_AMD_SCAN_DBG): 1 no filter, 2 no processing
+  uint32_t dbg;                  // profiling knobs (NGT_AMD_SCAN_DBG): 1 no filter, 2 no processing,
+                                 // 4 no first-tile bootstrap (wide kernel)
   unsigned long long* stats;     // or null: [0] candidates, [1] processing rounds, [2] tiles with candidates
   unsigned long long* gthr;      // [nq] smallest k-th key over the parts (all ones at launch)
   uint64_t* partial;             // [nq][nparts][k]
@@ -405,6 +406,10 @@ struct MfmaScanArgs {
 hipError_t launch_scan_prep(const ScanPrepArgs& a, bool cosine, bool query, hipStream_t s);
 hipError_t launch_scan_mfma(const MfmaScanArgs& a, int metric, int passes, hipStream_t s);
 size_t scan_mfma_lds_bytes(uint32_t k);
+// The same filter for 17 <= k <= 128 (scan_mfma_wide.hip): the (query, part)
+// lists are sorted in place in a.partial, the LDS does not grow with k.
+hipError_t launch_scan_mfma_wide(const MfmaScanArgs& a, int metric, int passes, hipStream_t s);
+size_t scan_mfma_wide_lds_bytes();
 
 // uint8 L2 exact scan on the int8 matrix cores (scan_u8.hip): Dp <= 1024 a
 // multiple of 16, k <= 16, query rows 16-byte aligned.

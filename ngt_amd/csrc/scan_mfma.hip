@@ -39,91 +39,18 @@
 
 #include "ngt_device.h"
 #include "ngt_kernels.h"
+#include "scan_mfma_common.h"
 #include "search_common.h"
 
 namespace ngt_amd {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int kMxQ = 128;    // queries per workgroup
-constexpr int kMxR = 256;    // rows per tile
-constexpr int kMxW = kMxR / 32;  // candidate bitmap words per query
 constexpr int kMxPend = 16;  // pending candidates per query between processing rounds
-constexpr int kMxNst = 4;    // staging ring depth (k-steps in flight: kMxNst - 1)
-constexpr int kMxStage = 24576;  // one k-step: rows hi/lo 8 KiB each, queries hi/lo 4 KiB each
 
 __device__ __forceinline__ uint16_t bf16_bits(float v) {
   const __bf16 b = (__bf16)v;
   return __builtin_bit_cast(uint16_t, b);
 }
 __device__ __forceinline__ float bf16_val(uint16_t u) { return __uint_as_float((uint32_t)u << 16); }
-
-// squared-sum bound of a distance d (as in scan_kernels.hip): any sum whose
-// (float)sqrt((double)sum) is <= d is below it
-__device__ __forceinline__ float scan_sq_bound(float d) {
-  if (!(d >= 0.0f) || d >= 3.0e38f) return __builtin_huge_valf();
-  const double dn = (double)__uint_as_float(__float_as_uint(d) + 1u);
-  const float s2 = (float)(dn * dn);
-  return __uint_as_float(__float_as_uint(s2) + 1u);
-}
-
-// The comparator on one lane: PrimitiveComparator's 16 AVX-512 accumulator
-// lanes as 16 registers (lane l: dims l, l+16, ...), the 16 -> 8 -> 4 folds
-// and (x0 + x1) + (x2 + x3) exactly as fold16 (ngt_device.h), double sqrt /
-// double cosine -- bit for bit dist_f32<M>.
-__device__ __forceinline__ float fold16_lane(const float* v) {
-  float t8[8], t4[4];
-#pragma unroll
-  for (int j = 0; j < 8; j++) t8[j] = v[j + 8] + v[j];
-#pragma unroll
-  for (int j = 0; j < 4; j++) t4[j] = t8[j + 4] + t8[j];
-  return (t4[0] + t4[1]) + (t4[2] + t4[3]);
-}
-template <int M>
-__device__ __forceinline__ float dist_lane(const float* __restrict__ q, const float* __restrict__ x, int dp) {
-  const float4* q4 = reinterpret_cast<const float4*>(q);
-  const float4* x4 = reinterpret_cast<const float4*>(x);
-  if constexpr (M == kL2) {
-    float acc[16];
-#pragma unroll
-    for (int l = 0; l < 16; l++) acc[l] = 0.0f;
-#pragma unroll 2
-    for (int i = 0; i < (dp >> 4); i++) {
-#pragma unroll
-      for (int c = 0; c < 4; c++) {
-        const float4 qv = q4[4 * i + c], xv = x4[4 * i + c];
-        const float d0 = qv.x - xv.x, d1 = qv.y - xv.y, d2 = qv.z - xv.z, d3 = qv.w - xv.w;
-        acc[4 * c + 0] = __builtin_fmaf(d0, d0, acc[4 * c + 0]);
-        acc[4 * c + 1] = __builtin_fmaf(d1, d1, acc[4 * c + 1]);
-        acc[4 * c + 2] = __builtin_fmaf(d2, d2, acc[4 * c + 2]);
-        acc[4 * c + 3] = __builtin_fmaf(d3, d3, acc[4 * c + 3]);
-      }
-    }
-    return (float)sqrt((double)fold16_lane(acc));
-  } else {  // kCosine
-    float na[16], nb[16], sv[16];
-#pragma unroll
-    for (int l = 0; l < 16; l++) na[l] = nb[l] = sv[l] = 0.0f;
-#pragma unroll 2
-    for (int i = 0; i < (dp >> 4); i++) {
-#pragma unroll
-      for (int c = 0; c < 4; c++) {
-        const float4 qv = q4[4 * i + c], xv = x4[4 * i + c];
-        const float qa[4] = {qv.x, qv.y, qv.z, qv.w}, xa[4] = {xv.x, xv.y, xv.z, xv.w};
-#pragma unroll
-        for (int e = 0; e < 4; e++) {
-          na[4 * c + e] = __builtin_fmaf(qa[e], qa[e], na[4 * c + e]);
-          nb[4 * c + e] = __builtin_fmaf(xa[e], xa[e], nb[4 * c + e]);
-          sv[4 * c + e] = __builtin_fmaf(xa[e], qa[e], sv[4 * c + e]);
-        }
-      }
-    }
-    const double dna = fold16_lane(na), dnb = fold16_lane(nb), ds = fold16_lane(sv);
-    const double cs = ds / sqrt(dna * dnb);
-    return (float)(1.0 - cs);
-  }
-}
 
 // ---------------------------------------------------------------------------
 // Operand preparation: one wave per 32-object tile.  Lane (h = l >> 5,
@@ -241,10 +168,6 @@ __global__ void __launch_bounds__(64) ngt_scan_prep_kernel(ScanPrepArgs a) {
 // ---------------------------------------------------------------------------
 // The scan.
 // ---------------------------------------------------------------------------
-// Workgroup barrier for LDS only.  __syncthreads() would also drain the
-// staging ring's LDS-DMA loads (vmcnt(0)); the ring is waited for by count.
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
 template <int M, int P>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
 ngt_scan_mfma_kernel(MfmaScanArgs a) {
