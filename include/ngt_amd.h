@@ -213,11 +213,12 @@ float ngt_amd_last_search_kernel_ms(const ngt_amd_index *index);
 int ngt_amd_last_search_filtered(const ngt_amd_index *index);
 /* The kernel of the latest exact scan (ngt_amd_linear_search[_device]) on the
  * index: 0 quad-per-row (every metric and type), 1 tiled FMA (float L2),
- * 2 bf16 matrix-core filter (float L2 / Cosine), 3 uint8 L2 on the int8
+ * 2 bf16 matrix-core filter (float L2 / Cosine / Angle / Normalized Angle /
+ * Normalized Cosine / Normalized L2), 3 uint8 L2 on the int8
  * matrix cores (batches of >= 32 queries, k <= 16, padded dimension <= 1024),
  * 4 uint8 L1 / Hamming on packed byte-SAD and popcount (batches of >= 32
  * queries, k <= 16, padded dimension <= 256), 5 the bf16 matrix-core filter
- * with lists of 17 .. 128 results (float L2 / Cosine, batches of >= 32
+ * with lists of 17 .. 128 results (the same float metrics, batches of >= 32
  * queries).  The last call on the index wins. */
 int ngt_amd_last_scan_kernel(const ngt_amd_index *index);
 /* The device error word of the launch context of `stream` (created on first

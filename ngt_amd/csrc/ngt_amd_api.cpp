@@ -959,6 +959,8 @@ extern "C" int ngt_amd_search(ngt_amd_index* ix, const ngt_amd_search_params* pr
 // accumulation of P dp + 16 terms < (P dp + 16) 2^-24 of the sum of
 // magnitudes; both doubled (Cosine: quadrupled, it also absorbs the
 // normalization), plus the comparator's own rounding (rho) where used.
+// The normalized metrics' filter value is the dot product alone: the doubled
+// bounds plus rho for the comparator's fp32 dot product, all times |q| Xmax.
 static int scan_passes() {
   static const int p = [] {
     const char* v = ngt_amd::knob("NGT_AMD_SCAN_PASSES");
@@ -966,11 +968,30 @@ static int scan_passes() {
   }();
   return p;
 }
+// the operand form of a metric (ngt_scan_prep_kernel)
+static int scan_form(const ngt_amd_index* ix) {
+  switch (ix->metric) {
+    case NGT_AMD_DISTANCE_COSINE:
+    case NGT_AMD_DISTANCE_ANGLE: return kScanPrepCos;
+    case NGT_AMD_DISTANCE_NORMALIZED_ANGLE:
+    case NGT_AMD_DISTANCE_NORMALIZED_COSINE:
+    case NGT_AMD_DISTANCE_NORMALIZED_L2: return kScanPrepDot;
+    default: return kScanPrepL2;
+  }
+}
+// Angle and the normalized metrics: their thresholds come from scan_dot_bound.h
+static bool scan_dot_family(const ngt_amd_index* ix) {
+  return ix->metric == NGT_AMD_DISTANCE_ANGLE || scan_form(ix) == kScanPrepDot;
+}
 static double scan_kappa(const ngt_amd_index* ix, int passes) {
   const double dp = (double)ix->dp;
   const double split = passes == 3 ? 3.2 * std::ldexp(1.0, -16) : 1.02 * std::ldexp(1.0, -7);
   const double base = split + (passes * dp + 64.0) * std::ldexp(1.0, -23);
-  return ix->metric == NGT_AMD_DISTANCE_COSINE ? 4.0 * base : 2.0 * base;
+  switch (scan_form(ix)) {
+    case kScanPrepCos: return 4.0 * base;
+    case kScanPrepDot: return 2.0 * base + ((double)ix->dp + 64.0) * std::ldexp(1.0, -22);
+    default: return 2.0 * base;
+  }
 }
 
 // The rows' bf16 hi/lo image in fragment order plus the norm column, built
@@ -999,7 +1020,7 @@ static int ensure_scan_rows(ngt_amd_index* ix, int passes, hipStream_t s) {
   p.one_minus_kappa = (float)(1.0 - kappa);
   p.kappa = (float)kappa;
   p.xmax_bits = ix->scan.xmax.p;
-  HIP_OK(launch_scan_prep(p, ix->metric == NGT_AMD_DISTANCE_COSINE, false, s));
+  HIP_OK(launch_scan_prep(p, scan_form(ix), false, s));
   // other streams may scan as soon as the version is published
   HIP_OK(hipStreamSynchronize(s));
   ix->scan.version = ix->rows_version;
@@ -1010,9 +1031,11 @@ static int ensure_scan_rows(ngt_amd_index* ix, int passes, hipStream_t s) {
 // wide: lists of 17 .. 128 results (scan_mfma_wide.hip) -- the same operands,
 // bounds, parts and merge; the kernel sorts its lists in place in `partial`.
 static int linear_search_mfma(ngt_amd_index* ix, SearchCtx* c, LinearArgs& a, hipStream_t s, bool wide = false) {
-  const int passes = scan_passes();
+  // the dot family has the 3-pass filter only; the rows' image is keyed by the passes
+  const bool dot = scan_dot_family(ix);
+  const int passes = dot ? 3 : scan_passes();
   if (ensure_scan_rows(ix, passes, s)) return -1;
-  const bool cosine = ix->metric == NGT_AMD_DISTANCE_COSINE;
+  const bool cosine = scan_form(ix) == kScanPrepCos;
   const uint32_t ks = ix->dp / 16 + 1;
   const uint32_t mblocks = (a.nq + 127) / 128;  // 128 queries per workgroup
   const uint64_t nqpad = (uint64_t)mblocks * 128;
@@ -1038,8 +1061,10 @@ static int linear_search_mfma(ngt_amd_index* ix, SearchCtx* c, LinearArgs& a, hi
   p.hm = c->shb.p + nqpad;
   // bootstrap margin: two filter errors plus the comparator's rounding
   const double rho = ((double)ix->dp + 64.0) * std::ldexp(1.0, -22);
-  p.kappa_boot = (float)(cosine ? 2.0 * kappa : kappa + rho);
-  HIP_OK(launch_scan_prep(p, cosine, true, s));
+  // (the dot family's margin is one filter error on each side of the finish: hm = E_q)
+  p.kappa_boot = (float)(dot ? kappa : cosine ? 2.0 * kappa : kappa + rho);
+  p.hb_cos = dot ? -p.kappa : 1.0f - p.kappa;
+  HIP_OK(launch_scan_prep(p, scan_form(ix), true, s));
 
   // One launch: every query block x floor(CUs / blocks) parts, at least one
   // and no more than the tiles (or the wide scan's test cap) -- one workgroup
@@ -1077,7 +1102,16 @@ static int linear_search_mfma(ngt_amd_index* ix, SearchCtx* c, LinearArgs& a, hi
   m.dp = (int)ix->dp;
   m.ntiles = ntiles;
   m.radius = a.radius;
-  if (cosine) {
+  m.fin = ix->metric;
+  if (dot) {
+    // the radius as a k-th distance: the smallest float at or above it
+    m.scale = 1.0f;
+    m.t_init = INFINITY;
+    if (a.radius >= 0.0 && a.radius < 3.0e38) {
+      m.t_init = (float)a.radius;
+      if ((double)m.t_init < a.radius) m.t_init = std::nextafterf(m.t_init, INFINITY);
+    }
+  } else if (cosine) {
     m.scale = 1.0f;
     m.t_init = a.radius < 0.0 || a.radius >= 3.0e38 ? INFINITY : (float)a.radius;
   } else {
@@ -1285,8 +1319,13 @@ extern "C" int ngt_amd_linear_search_device(ngt_amd_index* ix, const void* d_que
     const char* v = ngt_amd::knob("NGT_AMD_LINEAR_MFMA");
     return !(v && atoi(v) == 0);
   }();
-  if (use_mfma && nq >= 32 && ix->otype == NGT_AMD_OBJECT_FLOAT && k <= 16 &&
-      (ix->metric == NGT_AMD_DISTANCE_L2 || ix->metric == NGT_AMD_DISTANCE_COSINE)) {
+  // Angle and the normalized metrics take the same two kernels (their
+  // thresholds: scan_dot_bound.h); NGT_AMD_LINEAR_DOT=0, read per call, sends
+  // them back to the quad kernel.
+  const char* dot_knob = ngt_amd::knob("NGT_AMD_LINEAR_DOT");
+  const bool mfma_metric = ix->metric == NGT_AMD_DISTANCE_L2 || ix->metric == NGT_AMD_DISTANCE_COSINE ||
+                           (scan_dot_family(ix) && !(dot_knob && atoi(dot_knob) == 0));
+  if (use_mfma && nq >= 32 && ix->otype == NGT_AMD_OBJECT_FLOAT && k <= 16 && mfma_metric) {
     ix->last_scan = 2;
     return linear_search_mfma(ix, c, a, s);
   }
@@ -1295,7 +1334,7 @@ extern "C" int ngt_amd_linear_search_device(ngt_amd_index* ix, const void* d_que
   // rounds, so the LDS does not grow with k.  The knob is read per call.
   const char* wide_knob = ngt_amd::knob("NGT_AMD_LINEAR_WIDE");
   if (use_mfma && !(wide_knob && atoi(wide_knob) == 0) && nq >= 32 && ix->otype == NGT_AMD_OBJECT_FLOAT && k >= 17 &&
-      k <= 128 && (ix->metric == NGT_AMD_DISTANCE_L2 || ix->metric == NGT_AMD_DISTANCE_COSINE)) {
+      k <= 128 && mfma_metric) {
     ix->last_scan = 5;
     return linear_search_mfma(ix, c, a, s, true);
   }

@@ -376,6 +376,7 @@ struct ScanPrepArgs {
   uint16_t* out_h;
   uint16_t* out_l;
   float one_minus_kappa, kappa, slack, kappa_boot;
+  float hb_cos;                  // queries, kScanPrepCos: the filter base (Cosine 1 - kappa, Angle -kappa)
   uint32_t* xmax_bits;           // rows: atomicMax target; queries: read
   float* hb;                     // queries: [n_pad] filter base
   float* hm;                     // queries: [n_pad] bootstrap margin
@@ -402,9 +403,14 @@ struct MfmaScanArgs {
   unsigned long long* stats;     // or null: [0] candidates, [1] processing rounds, [2] tiles with candidates
   unsigned long long* gthr;      // [nq] smallest k-th key over the parts (all ones at launch)
   uint64_t* partial;             // [nq][nparts][k]
+  int fin;                       // the normalized metrics' one instantiation: which finish (the metric)
 };
-hipError_t launch_scan_prep(const ScanPrepArgs& a, bool cosine, bool query, hipStream_t s);
+// the operand forms of ngt_scan_prep_kernel
+enum { kScanPrepL2 = 0, kScanPrepCos = 1, kScanPrepDot = 2 };
+hipError_t launch_scan_prep(const ScanPrepArgs& a, int form, bool query, hipStream_t s);
+// metric: L2 and Cosine (passes 3 or 1); Angle and the normalized three (3)
 hipError_t launch_scan_mfma(const MfmaScanArgs& a, int metric, int passes, hipStream_t s);
+hipError_t launch_scan_mfma_dot(const MfmaScanArgs& a, int metric, size_t lds, uint32_t grid, hipStream_t s);
 size_t scan_mfma_lds_bytes(uint32_t k);
 // The same filter for 17 <= k <= 128 (scan_mfma_wide.hip): the (query, part)
 // lists are sorted in place in a.partial, the LDS does not grow with k.

@@ -1,6 +1,9 @@
 // scan_mfma.hip -- the exact batch scan of ObjectSpaceRepository::linearSearch
 // (lib/NGT/ObjectSpaceRepository.h:466-502) for float L2 and Cosine as a
-// matrix-core filter plus a bit-exact recompute.
+// matrix-core filter plus a bit-exact recompute.  The kernel template is in
+// scan_mfma_kernel.h; this file instantiates it for L2 and Cosine and holds
+// the operand preparation, scan_mfma_dot.hip instantiates it for Angle and the
+// normalized metrics (thresholds: scan_dot_bound.h).
 //
 // Every (row, query) pair gets a dot product from bf16 MFMAs
 // (v_mfma_f32_32x32x16_bf16): rows and queries are split into bf16 hi + lo
@@ -37,14 +40,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "ngt_device.h"
-#include "ngt_kernels.h"
-#include "scan_mfma_common.h"
-#include "search_common.h"
+#include "scan_mfma_kernel.h"
 
 namespace ngt_amd {
-
-constexpr int kMxPend = 16;  // pending candidates per query between processing rounds
 
 __device__ __forceinline__ uint16_t bf16_bits(float v) {
   const __bf16 b = (__bf16)v;
@@ -56,8 +54,13 @@ __device__ __forceinline__ float bf16_val(uint16_t u) { return __uint_as_float((
 // Operand preparation: one wave per 32-object tile.  Lane (h = l >> 5,
 // r = l & 31) writes, per k-step s, dims 16s + 8h .. +7 of object 32t + r.
 // ---------------------------------------------------------------------------
-template <bool COS, bool QUERY>
+// F: kScanPrepL2 (the norm column carries |x|^2 (1 - kappa)), kScanPrepCos
+// (both sides normalized, zero norms forced; Cosine and Angle) or kScanPrepDot
+// (the normalized metrics: operands as they are, the column carries only the
+// NaN / -inf flags, hb = -E_q and hm = E_q with E_q = kappa |q| Xmax + slack).
+template <int F, bool QUERY>
 __global__ void __launch_bounds__(64) ngt_scan_prep_kernel(ScanPrepArgs a) {
+  constexpr bool COS = F == kScanPrepCos, DOT = F == kScanPrepDot;
   const int lane = threadIdx.x;
   const int r = lane & 31, h = lane >> 5;
   const int nk = a.dp >> 4;
@@ -122,7 +125,7 @@ __global__ void __launch_bounds__(64) ngt_scan_prep_kernel(ScanPrepArgs a) {
         ev[0] = 0x7fc0;  // NaN: never a candidate
       } else if (forced) {
         ev[0] = 0xff80;  // -inf: v' = +inf, always a candidate
-      } else if (!COS) {
+      } else if (!COS && !DOT) {
         const float xnk = ss * a.one_minus_kappa;
         ev[0] = bf16_bits(xnk);
         const float r1 = xnk - bf16_val(ev[0]);
@@ -151,8 +154,13 @@ __global__ void __launch_bounds__(64) ngt_scan_prep_kernel(ScanPrepArgs a) {
       } else if (forced) {
         hb = -__builtin_huge_valf();
       } else if (COS) {
-        hb = 1.0f - a.kappa;
+        hb = a.hb_cos;
         hm = a.kappa_boot;
+      } else if (DOT) {
+        const float xmax = __uint_as_float(*a.xmax_bits);
+        const float nq = sqrtf(ss) * 1.0000005f;
+        hm = a.kappa * nq * xmax + a.slack;
+        hb = -hm;
       } else {
         const float xmax = __uint_as_float(*a.xmax_bits);
         const float nq = sqrtf(ss) * 1.0000005f;
@@ -165,388 +173,25 @@ __global__ void __launch_bounds__(64) ngt_scan_prep_kernel(ScanPrepArgs a) {
   }
 }
 
-// ---------------------------------------------------------------------------
-// The scan.
-// ---------------------------------------------------------------------------
-template <int M, int P>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
-ngt_scan_mfma_kernel(MfmaScanArgs a) {
-  extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-  const uint32_t k = a.k;
-  uint8_t* stage = smem;                                              // [4][24 KiB] ring
-  uint64_t* lists = reinterpret_cast<uint64_t*>(smem + kMxNst * kMxStage);  // [256][k]
-  uint64_t* thr = lists + (size_t)kMxQ * k;                            // [256] k-th key or ~0
-  uint32_t* pend = reinterpret_cast<uint32_t*>(thr + kMxQ);           // [128][16] pending rows
-  float* boot = reinterpret_cast<float*>(pend);                        // [128][16] (first tile, before any pending)
-  float* pdist = reinterpret_cast<float*>(pend + kMxQ * kMxPend);      // [128][16] their distances
-  float* H = pdist + kMxQ * kMxPend;                                   // [128]
-  float* HB = H + kMxQ;                                                // [256]
-  float* HM = HB + kMxQ;                                               // [256]
-  uint32_t* cnt = reinterpret_cast<uint32_t*>(HM + kMxQ);             // [256] list sizes
-  uint32_t* pc = cnt + kMxQ;                                           // [256] pending counts
-  uint32_t* bits = pc + kMxQ;                                          // [256][4]
-  uint32_t* flags = bits + kMxQ * kMxW;                                // [4]
-
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int wr = w & 1, wq = w >> 1;
-  // the launch covers query blocks mb0 .. mb0 + mblocks - 1; its parts are
-  // a multiple of 8 and part p runs on XCD p % 8 (blockIdx % 8 picks the
-  // XCD), so the workgroups streaming one part share that XCD's L2
-  const uint32_t slot = a.xcd ? blockIdx.x >> 3 : blockIdx.x;
-  const uint32_t mb = a.mb0 + slot % a.mblocks;
-  const uint32_t part = a.xcd ? (slot / a.mblocks) * 8 + (blockIdx.x & 7) : slot / a.mblocks;
-  const uint32_t q0 = mb * kMxQ;
-  const uint32_t t0 = part * a.tiles_per_part;
-  uint32_t t1 = t0 + a.tiles_per_part;
-  if (t1 > a.ntiles) t1 = a.ntiles;
-  const uint32_t ks = a.ks;
-  const uint64_t row0 = (uint64_t)t0 * kMxR;  // pending rows are offsets from here
-
-  for (int i = tid; i < kMxQ; i += 256) {
-    thr[i] = ~0ull;
-    cnt[i] = 0;
-    pc[i] = 0;
-    HB[i] = a.hb[q0 + i];
-    HM[i] = a.hm[q0 + i];
-    H[i] = HB[i] - a.scale * a.t_init;
-  }
-  for (int i = tid; i < kMxQ * kMxW; i += 256) bits[i] = 0;
-  if (tid < 4) flags[tid] = 0;
-
-  // The comparator's distances of every pending (query, row), then their
-  // insertion into the k-lists (one thread per query) and the new filter
-  // thresholds.  Called by the whole workgroup.
-  auto process = [&]() {
-    {  // the comparator's distances: two threads per query
-      const uint32_t q = tid & (kMxQ - 1);
-      const uint32_t n = min(pc[q], (uint32_t)kMxPend);
-      if (n) {
-        const float* qp = reinterpret_cast<const float*>(a.queries + (uint64_t)(q0 + q) * a.query_bytes);
-        for (uint32_t ci = tid >> 7; ci < n; ci += 2) {
-          const uint64_t row = row0 + pend[q * kMxPend + ci];
-          pdist[q * kMxPend + ci] =
-              dist_lane<M>(qp, reinterpret_cast<const float*>(a.rows + row * a.row_bytes), a.dp);
-        }
-      }
-    }
-    lds_barrier();
-    if (tid < kMxQ && pc[tid]) {
-      const uint32_t n = min(pc[tid], (uint32_t)kMxPend);
-      uint32_t c = cnt[tid];
-      uint64_t* L = lists + (size_t)tid * k;
-      uint64_t th = thr[tid];
-      for (uint32_t ci = 0; ci < n; ci++) {
-        const float d = pdist[tid * kMxPend + ci];
-        if (!(a.radius < 0.0 || (double)d <= a.radius)) continue;
-        const uint64_t key = make_key(d, (uint32_t)(row0 + pend[tid * kMxPend + ci]));
-        if (key >= th) continue;
-        bool dup = false;  // a pair seen again on the bitmap path
-        for (uint32_t j = 0; j < c; j++) dup = dup || L[j] == key;
-        if (dup) continue;
-        uint32_t p = c < k ? c : k - 1;  // the k-th entry drops out when full
-        while (p > 0 && L[p - 1] > key) {
-          L[p] = L[p - 1];
-          p--;
-        }
-        L[p] = key;
-        if (c < k) c++;
-        if (c >= k) th = L[k - 1];
-      }
-      if (a.stats) atomicAdd(&a.stats[0], (unsigned long long)n);
-      pc[tid] = 0;
-      thr[tid] = th;
-      cnt[tid] = c;
-    }
-    if (tid < kMxQ && q0 + tid < a.nq) {
-      // every part's k-th key bounds the query's global k-th key: publish
-      // this part's, take the smallest over the parts for the filter
-      const uint64_t th = thr[tid];
-      const uint64_t g = __hip_atomic_fetch_min(a.gthr + q0 + tid, (unsigned long long)th, __ATOMIC_RELAXED,
-                                                __HIP_MEMORY_SCOPE_AGENT);
-      const uint64_t best = g < th ? g : th;
-      if (best != ~0ull) {
-        const float kd = key_dist(best);
-        const float tv = M == kL2 ? fminf(a.t_init, scan_sq_bound(kd)) : fminf(a.t_init, kd);
-        H[tid] = fmaxf(H[tid], HB[tid] - a.scale * tv);
-      }
-    }
-    if (a.stats && tid == 0) atomicAdd(&a.stats[1], 1ull);
-    lds_barrier();
-  };
-
-  // staging ring: k-step g of the part (tile t0 + g / ks, k-step g % ks)
-  // goes to slot g % 4 by LDS-DMA; wave w moves blocks w, 4 + w, ... of the
-  // 24 1-KiB blocks (rows hi, rows lo: 8 tiles each; queries hi, lo: 4
-  // tiles each), so the image is the fragment order of the HBM arrays
-  typedef __attribute__((address_space(3))) void* lds_ptr;
-  const uint32_t G = (t1 > t0 ? t1 - t0 : 0) * ks;
-  auto issue = [&](uint32_t g) {
-    uint8_t* base = stage + (g % kMxNst) * kMxStage + w * 1024;
-    const uint32_t gg = g < G ? g : G - 1;  // past the end: a harmless reload
-    const uint32_t rt = t0 + gg / ks, s = gg - (gg / ks) * ks;
-    const size_t ro0 = (((size_t)rt * 8 + w) * ks + s) * 512 + (size_t)lane * 8;
-    const size_t ro1 = ro0 + (size_t)4 * ks * 512;
-    const size_t qo = (((size_t)mb * 4 + w) * ks + s) * 512 + (size_t)lane * 8;
-    __builtin_amdgcn_global_load_lds((const void*)(a.rh + ro0), (lds_ptr)(base), 16, 0, 0);
-    __builtin_amdgcn_global_load_lds((const void*)(a.rh + ro1), (lds_ptr)(base + 4096), 16, 0, 0);
-    __builtin_amdgcn_global_load_lds((const void*)(a.qh + qo), (lds_ptr)(base + 16384), 16, 0, 0);
-    if (P == 3) {  // the lo parts
-      __builtin_amdgcn_global_load_lds((const void*)(a.rl + ro0), (lds_ptr)(base + 8192), 16, 0, 0);
-      __builtin_amdgcn_global_load_lds((const void*)(a.rl + ro1), (lds_ptr)(base + 12288), 16, 0, 0);
-      __builtin_amdgcn_global_load_lds((const void*)(a.ql + qo), (lds_ptr)(base + 20480), 16, 0, 0);
-    }
-  };
-
-  f32x16 acc[4][2];
-#pragma unroll
-  for (int mt = 0; mt < 4; mt++)
-#pragma unroll
-    for (int nt = 0; nt < 2; nt++) acc[mt][nt] = (f32x16){};
-
-  __syncthreads();
-  if (G) {
-    issue(0);
-    issue(1);
-    issue(2);
-  }
-  const int ql0 = wq * 64 + (lane & 31);  // this lane's query in n-tile 0
-  const int rsh = 4 * (lane >> 5);
-  for (uint32_t g = 0; g < G; g++) {
-    const uint32_t rt = t0 + g / ks, s = g - (g / ks) * ks;
-    // k-step g has landed once at most k-steps g+1, g+2 (2P loads each) are
-    // outstanding; the barrier publishes every wave's blocks and retires the
-    // reads of slot (g + 3) % 4, which is refilled right after
-    if (P == 3) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    lds_barrier();
-    issue(g + 3);
-    // hi x hi + hi x lo + lo x hi (the norm column's lo parts are 0)
-    {
-      const uint8_t* sb = stage + (g % kMxNst) * kMxStage + lane * 16;
-      bf16x8 ah[4], al[4], bh[2], bl[2];
-#pragma unroll
-      for (int mt = 0; mt < 4; mt++) {
-        ah[mt] = *reinterpret_cast<const bf16x8*>(sb + (wr * 4 + mt) * 1024);
-        if (P == 3) al[mt] = *reinterpret_cast<const bf16x8*>(sb + 8192 + (wr * 4 + mt) * 1024);
-      }
-#pragma unroll
-      for (int nt = 0; nt < 2; nt++) {
-        bh[nt] = *reinterpret_cast<const bf16x8*>(sb + 16384 + (wq * 2 + nt) * 1024);
-        if (P == 3) bl[nt] = *reinterpret_cast<const bf16x8*>(sb + 20480 + (wq * 2 + nt) * 1024);
-      }
-#pragma unroll
-      for (int mt = 0; mt < 4; mt++)
-#pragma unroll
-        for (int nt = 0; nt < 2; nt++) {
-          acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[mt], bh[nt], acc[mt][nt], 0, 0, 0);
-          if (P == 3) {
-            acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[mt], bl[nt], acc[mt][nt], 0, 0, 0);
-            acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[mt], bh[nt], acc[mt][nt], 0, 0, 0);
-          }
-        }
-    }
-    if (s + 1 < ks) continue;
-
-    if (a.dbg & 1) {
-#pragma unroll
-      for (int mt = 0; mt < 4; mt++)
-#pragma unroll
-        for (int nt = 0; nt < 2; nt++) acc[mt][nt] = (f32x16){};
-      continue;
-    }
-    if (rt == t0) {
-      // bootstrap: the k-th largest of 16 filter values of distinct rows
-      // (each lane's 4 largest finite ones of its 32) bounds the k-th
-      // distance from above; rows more than the margin HM below it cannot
-      // make the top k
-#pragma unroll
-      for (int nt = 0; nt < 2; nt++) {
-        float t4[4] = {-__builtin_huge_valf(), -__builtin_huge_valf(), -__builtin_huge_valf(),
-                       -__builtin_huge_valf()};
-#pragma unroll
-        for (int mt = 0; mt < 4; mt++)
-#pragma unroll
-          for (int e = 0; e < 16; e++) {
-            float v = acc[mt][nt][e];
-            if (!(v < __builtin_huge_valf())) v = -__builtin_huge_valf();  // NaN, +inf
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-              const float hi = fmaxf(t4[j], v), lo = fminf(t4[j], v);
-              t4[j] = hi;
-              v = lo;
-            }
-          }
-        float* bp = boot + (ql0 + nt * 32) * 16 + (wr * 2 + (lane >> 5)) * 4;
-#pragma unroll
-        for (int j = 0; j < 4; j++) bp[j] = t4[j];
-      }
-      lds_barrier();
-      if (tid < kMxQ && q0 + tid < a.nq) {
-        float v[16];
-#pragma unroll
-        for (int j = 0; j < 16; j++) v[j] = boot[tid * 16 + j];
-        // k-th largest: k - 1 passes of removing the maximum
-        float kth = -__builtin_huge_valf();
-        for (uint32_t r = 0; r < k; r++) {
-          float mx = -__builtin_huge_valf();
-          int at = 0;
-#pragma unroll
-          for (int j = 0; j < 16; j++)
-            if (v[j] > mx) {
-              mx = v[j];
-              at = j;
-            }
-          kth = mx;
-#pragma unroll
-          for (int j = 0; j < 16; j++)
-            if (j == at) v[j] = -__builtin_huge_valf();
-        }
-        const float hb = kth - HM[tid];
-        if (hb > H[tid]) H[tid] = hb;
-      }
-      lds_barrier();
-    }
-
-    // ---- filter: lane holds queries ql0 + 32 nt x 64 rows of the tile.
-    // Fast path: a 16-value block whose maximum is below the threshold is
-    // done in 8 VALU operations; passing values go straight into the query's
-    // pending slots (LDS atomics).  A full slot array falls back to the
-    // candidate bitmap below.
-    float hq[2];
-#pragma unroll
-    for (int nt = 0; nt < 2; nt++) hq[nt] = H[ql0 + nt * 32];
-    const uint32_t rbase = (rt - t0) * kMxR + wr * 128 + rsh;
-#pragma unroll
-    for (int mt = 0; mt < 4; mt++)
-#pragma unroll
-      for (int nt = 0; nt < 2; nt++) {
-        float mx = acc[mt][nt][0];
-#pragma unroll
-        for (int e = 1; e < 16; e++) mx = fmaxf(mx, acc[mt][nt][e]);
-        const bool hit = mx >= hq[nt];
-        if (__ballot(hit)) {
-          if (hit) {
-            const uint32_t q = ql0 + nt * 32;
-#pragma unroll
-            for (int e = 0; e < 16; e++)
-              if (acc[mt][nt][e] >= hq[nt]) {
-                const uint32_t n = atomicAdd(&pc[q], 1u);
-                if (n < (uint32_t)kMxPend) pend[q * kMxPend + n] = rbase + mt * 32 + (e & 3) + 8 * (e >> 2);
-                if (n + 4 >= (uint32_t)kMxPend) flags[1] = 1;  // process after this tile
-                if (n >= (uint32_t)kMxPend) flags[2] = 1;      // overflow: bitmap path
-              }
-          }
-        }
-      }
-    lds_barrier();
-    const uint32_t now = flags[1], over = flags[2];
-    lds_barrier();
-    if (tid == 0) flags[1] = flags[2] = 0;
-    if (a.stats && tid == 0 && now) atomicAdd(&a.stats[2], 1ull);
-    if (now && !(a.dbg & 2)) {
-      if (tid < kMxQ && pc[tid] > (uint32_t)kMxPend) pc[tid] = kMxPend;
-      lds_barrier();
-      process();
-      if (over) {
-        // some passing pairs found no slot: redo the tile through the
-        // candidate bitmap with the tightened thresholds (pairs already
-        // processed are skipped at insertion, every round takes new bits)
-#pragma unroll
-        for (int nt = 0; nt < 2; nt++) hq[nt] = H[ql0 + nt * 32];
-#pragma unroll
-        for (int mt = 0; mt < 4; mt++)
-#pragma unroll
-          for (int nt = 0; nt < 2; nt++) {
-            uint32_t mask = 0;
-#pragma unroll
-            for (int e = 0; e < 16; e++)
-              mask |= (acc[mt][nt][e] >= hq[nt] ? 1u : 0u) << ((e & 3) + 8 * (e >> 2) + rsh);
-            if (mask) atomicOr(&bits[(ql0 + nt * 32) * kMxW + wr * 4 + mt], mask);
-          }
-        lds_barrier();
-        for (;;) {
-          if (tid < kMxQ) {
-            uint32_t n = 0;
-            bool rest = false;
-#pragma unroll
-            for (int wd = 0; wd < kMxW; wd++) {
-              uint32_t b = bits[tid * kMxW + wd];
-              while (b && n < (uint32_t)kMxPend) {
-                pend[tid * kMxPend + n++] = (uint32_t)((rt - t0) * kMxR) + wd * 32 + (__ffs(b) - 1);
-                b &= b - 1;
-              }
-              bits[tid * kMxW + wd] = b;
-              rest = rest || b != 0;
-            }
-            pc[tid] = n;
-            if (rest) flags[2] = 1;
-          }
-          lds_barrier();
-          const uint32_t more = flags[2];
-          lds_barrier();
-          if (tid == 0) flags[2] = 0;
-          process();
-          if (!more) break;
-          // drop the bits the tightened thresholds now exclude
-#pragma unroll
-          for (int nt = 0; nt < 2; nt++) hq[nt] = H[ql0 + nt * 32];
-#pragma unroll
-          for (int mt = 0; mt < 4; mt++)
-#pragma unroll
-            for (int nt = 0; nt < 2; nt++) {
-              uint32_t fail = 0;
-#pragma unroll
-              for (int e = 0; e < 16; e++)
-                fail |= (acc[mt][nt][e] >= hq[nt] ? 0u : 1u) << ((e & 3) + 8 * (e >> 2) + rsh);
-              if (fail) atomicAnd(&bits[(ql0 + nt * 32) * kMxW + wr * 4 + mt], ~fail);
-            }
-          lds_barrier();
-        }
-      }
-    }
-#pragma unroll
-    for (int mt = 0; mt < 4; mt++)
-#pragma unroll
-      for (int nt = 0; nt < 2; nt++) acc[mt][nt] = (f32x16){};
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  process();  // what is still pending at the part's end
-  for (uint32_t i = tid; i < (uint32_t)kMxQ * k; i += 256) {
-    const uint32_t ql = i / k, r = i - ql * k;
-    const uint32_t qi = q0 + ql;
-    if (qi < a.nq)
-      a.partial[((uint64_t)(qi - a.mb0 * kMxQ) * a.nparts + part) * k + r] = r < cnt[ql] ? lists[i] : ~0ull;
-  }
-}
-
 size_t scan_mfma_lds_bytes(uint32_t k) {
   return kMxNst * kMxStage + (size_t)kMxQ * k * 8 + kMxQ * 8 + (size_t)kMxQ * kMxPend * 8 + kMxQ * 4 * 5 +
          kMxQ * kMxW * 4 + 16;
 }
 
-hipError_t launch_scan_prep(const ScanPrepArgs& a, bool cosine, bool query, hipStream_t s) {
-  const uint64_t blocks = a.ntiles32 < 65536 ? a.ntiles32 : 65536;
-  if (blocks == 0) return hipSuccess;
-  if (cosine) {
-    if (query) hipLaunchKernelGGL((ngt_scan_prep_kernel<true, true>), dim3((uint32_t)blocks), dim3(64), 0, s, a);
-    else hipLaunchKernelGGL((ngt_scan_prep_kernel<true, false>), dim3((uint32_t)blocks), dim3(64), 0, s, a);
-  } else {
-    if (query) hipLaunchKernelGGL((ngt_scan_prep_kernel<false, true>), dim3((uint32_t)blocks), dim3(64), 0, s, a);
-    else hipLaunchKernelGGL((ngt_scan_prep_kernel<false, false>), dim3((uint32_t)blocks), dim3(64), 0, s, a);
-  }
-  return hipGetLastError();
+template <int F>
+static void launch_scan_prep_t(const ScanPrepArgs& a, bool query, uint32_t blocks, hipStream_t s) {
+  if (query) hipLaunchKernelGGL((ngt_scan_prep_kernel<F, true>), dim3(blocks), dim3(64), 0, s, a);
+  else hipLaunchKernelGGL((ngt_scan_prep_kernel<F, false>), dim3(blocks), dim3(64), 0, s, a);
 }
 
-template <int M, int P>
-static void launch_scan_mfma_t(const MfmaScanArgs& a, size_t lds, uint32_t grid, hipStream_t s) {
-  static bool attr = [] {
-    (void)hipFuncSetAttribute((const void*)ngt_scan_mfma_kernel<M, P>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              160 * 1024);
-    return true;
-  }();
-  (void)attr;
-  hipLaunchKernelGGL((ngt_scan_mfma_kernel<M, P>), dim3(grid), dim3(256), lds, s, a);
+hipError_t launch_scan_prep(const ScanPrepArgs& a, int form, bool query, hipStream_t s) {
+  const uint64_t blocks = a.ntiles32 < 65536 ? a.ntiles32 : 65536;
+  if (blocks == 0) return hipSuccess;
+  if (form == kScanPrepCos) launch_scan_prep_t<kScanPrepCos>(a, query, (uint32_t)blocks, s);
+  else if (form == kScanPrepDot) launch_scan_prep_t<kScanPrepDot>(a, query, (uint32_t)blocks, s);
+  else if (form == kScanPrepL2) launch_scan_prep_t<kScanPrepL2>(a, query, (uint32_t)blocks, s);
+  else return hipErrorNotSupported;
+  return hipGetLastError();
 }
 
 hipError_t launch_scan_mfma(const MfmaScanArgs& a, int metric, int passes, hipStream_t s) {
@@ -556,6 +201,9 @@ hipError_t launch_scan_mfma(const MfmaScanArgs& a, int metric, int passes, hipSt
   else if (metric == kL2 && passes == 1) launch_scan_mfma_t<kL2, 1>(a, lds, grid, s);
   else if (metric == kCosine && passes == 3) launch_scan_mfma_t<kCosine, 3>(a, lds, grid, s);
   else if (metric == kCosine && passes == 1) launch_scan_mfma_t<kCosine, 1>(a, lds, grid, s);
+  else if (passes == 3 && (metric == kAngle || metric == kNormalizedAngle || metric == kNormalizedCosine ||
+                           metric == kNormalizedL2))
+    return launch_scan_mfma_dot(a, metric, lds, grid, s);  // scan_mfma_dot.hip
   else return hipErrorNotSupported;
   return hipGetLastError();
 }

@@ -7,8 +7,19 @@
 #include <stdint.h>
 
 #include "ngt_device.h"
+#include "scan_dot_bound.h"
 
 namespace ngt_amd {
+
+// The dot family: metrics whose distance is a function of one dot product
+// (kScanDot: Normalized Cosine / L2 / Angle, one instantiation, the finish
+// picked at run time by MfmaScanArgs::fin) or of the comparator's cosine
+// (kAngle).  Their thresholds come from scan_dot_bound.h.
+constexpr int kScanDot = 1000;  // no metric's number
+template <int M>
+constexpr bool kIsDotFamily = M == kScanDot || M == kAngle;
+static_assert(kDotAngle == kAngle && kDotNormalizedAngle == kNormalizedAngle &&
+              kDotNormalizedCosine == kNormalizedCosine && kDotNormalizedL2 == kNormalizedL2);
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -31,7 +42,9 @@ __device__ __forceinline__ float scan_sq_bound(float d) {
 // The comparator on one lane: PrimitiveComparator's 16 AVX-512 accumulator
 // lanes as 16 registers (lane l: dims l, l+16, ...), the 16 -> 8 -> 4 folds
 // and (x0 + x1) + (x2 + x3) exactly as fold16 (ngt_device.h), double sqrt /
-// double cosine -- bit for bit dist_f32<M>.
+// double cosine -- bit for bit dist_f32<M>.  kScanDot: the one dot product
+// of the normalized metrics, its last four lanes summed in double (fold16_dot), and the
+// finish of metric `fin`.
 __device__ __forceinline__ float fold16_lane(const float* v) {
   float t8[8], t4[4];
 #pragma unroll
@@ -41,7 +54,8 @@ __device__ __forceinline__ float fold16_lane(const float* v) {
   return (t4[0] + t4[1]) + (t4[2] + t4[3]);
 }
 template <int M>
-__device__ __forceinline__ float dist_lane(const float* __restrict__ q, const float* __restrict__ x, int dp) {
+__device__ __forceinline__ float dist_lane(const float* __restrict__ q, const float* __restrict__ x, int dp,
+                                           int fin = 0) {
   const float4* q4 = reinterpret_cast<const float4*>(q);
   const float4* x4 = reinterpret_cast<const float4*>(x);
   if constexpr (M == kL2) {
@@ -61,7 +75,28 @@ __device__ __forceinline__ float dist_lane(const float* __restrict__ q, const fl
       }
     }
     return (float)sqrt((double)fold16_lane(acc));
-  } else {  // kCosine
+  } else if constexpr (M == kScanDot) {
+    float sv[16];
+#pragma unroll
+    for (int l = 0; l < 16; l++) sv[l] = 0.0f;
+#pragma unroll 2
+    for (int i = 0; i < (dp >> 4); i++) {
+#pragma unroll
+      for (int c = 0; c < 4; c++) {
+        const float4 qv = q4[4 * i + c], xv = x4[4 * i + c];
+        sv[4 * c + 0] = __builtin_fmaf(xv.x, qv.x, sv[4 * c + 0]);
+        sv[4 * c + 1] = __builtin_fmaf(xv.y, qv.y, sv[4 * c + 1]);
+        sv[4 * c + 2] = __builtin_fmaf(xv.z, qv.z, sv[4 * c + 2]);
+        sv[4 * c + 3] = __builtin_fmaf(xv.w, qv.w, sv[4 * c + 3]);
+      }
+    }
+    float t8[8], t4[4];
+#pragma unroll
+    for (int j = 0; j < 8; j++) t8[j] = sv[j + 8] + sv[j];
+#pragma unroll
+    for (int j = 0; j < 4; j++) t4[j] = t8[j + 4] + t8[j];
+    return dot_finish(fin, ((double)t4[0] + (double)t4[1]) + ((double)t4[2] + (double)t4[3]));
+  } else {  // kCosine, kAngle
     float na[16], nb[16], sv[16];
 #pragma unroll
     for (int l = 0; l < 16; l++) na[l] = nb[l] = sv[l] = 0.0f;
@@ -81,8 +116,21 @@ __device__ __forceinline__ float dist_lane(const float* __restrict__ q, const fl
     }
     const double dna = fold16_lane(na), dnb = fold16_lane(nb), ds = fold16_lane(sv);
     const double cs = ds / sqrt(dna * dnb);
-    return (float)(1.0 - cs);
+    if constexpr (M == kAngle) return dot_finish(kAngle, cs);
+    else return (float)(1.0 - cs);
   }
+}
+
+// The dot family's filter threshold of a k-th distance (or radius bound) kd:
+// H = T(kd) - E_q rounded down, with hb = -E_q (NaN: no such query, -inf: a
+// query the filter cannot bound -- both carry through).
+__device__ __forceinline__ float scan_dot_h(int fin, float hb, float kd) {
+  return dot_filter_threshold(dot_threshold(fin, kd), hb);
+}
+// The bootstrap: k rows have a filter value of at least v, so a comparator dot
+// product of at least v - hm (hm = E_q) and a distance of at most its finish.
+__device__ __forceinline__ float scan_dot_boot(int fin, float hb, float hm, float v) {
+  return scan_dot_h(fin, hb, dot_finish(fin, (double)v - (double)hm));
 }
 
 // Workgroup barrier for LDS only.  __syncthreads() would also drain the

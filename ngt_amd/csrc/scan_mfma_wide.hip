@@ -1,5 +1,7 @@
 // scan_mfma_wide.hip -- the matrix-core filtered exact scan (scan_mfma.hip)
-// for lists of 17 .. 128 results: float L2 and Cosine, >= 32 queries.
+// for lists of 17 .. 128 results: float L2, Cosine, Angle and the normalized
+// metrics (the latter four: 3-pass filter, thresholds from scan_dot_bound.h),
+// >= 32 queries.
 //
 // The filter is scan_mfma.hip's: the same fragment-ordered bf16 hi + lo row
 // image and query operands, the same extra k-step, the same H_q, kappa, rho
@@ -71,6 +73,8 @@ ngt_scan_mfma_wide_kernel(MfmaScanArgs a) {
   if (t1 > a.ntiles) t1 = a.ntiles;
   const uint32_t ks = a.ks;
   const uint64_t row0 = (uint64_t)t0 * kMxR;  // pending rows are offsets from here
+  // the dot family's finish and threshold rule (scan_dot_bound.h)
+  [[maybe_unused]] const int fin = M == kAngle ? (int)kAngle : a.fin;
 
   // the list of the workgroup's query ql in this part
   auto list_of = [&](uint32_t ql) -> uint64_t* {
@@ -83,7 +87,8 @@ ngt_scan_mfma_wide_kernel(MfmaScanArgs a) {
     pc[i] = 0;
     HB[i] = a.hb[q0 + i];
     HM[i] = a.hm[q0 + i];
-    H[i] = HB[i] - a.scale * a.t_init;
+    if constexpr (kIsDotFamily<M>) H[i] = scan_dot_h(fin, HB[i], a.t_init);
+    else H[i] = HB[i] - a.scale * a.t_init;
   }
   for (int i = tid; i < kMxQ * kMxW; i += 256) bits[i] = 0;
   for (int i = tid; i < 3 * kMxQ; i += 256) bcnt[i] = 0;
@@ -123,7 +128,7 @@ ngt_scan_mfma_wide_kernel(MfmaScanArgs a) {
       if ((uint32_t)lane < n) {
         const uint64_t row = row0 + pend[q * kWdPend + lane];
         const float d = dist_lane<M>(reinterpret_cast<const float*>(a.queries + (uint64_t)(q0 + q) * a.query_bytes),
-                                     reinterpret_cast<const float*>(a.rows + row * a.row_bytes), a.dp);
+                                     reinterpret_cast<const float*>(a.rows + row * a.row_bytes), a.dp, fin);
         if (a.radius < 0.0 || (double)d <= a.radius) {
           key = make_key(d, (uint32_t)row);
           ok = key < th;
@@ -186,8 +191,12 @@ ngt_scan_mfma_wide_kernel(MfmaScanArgs a) {
       const uint64_t best = g < th ? g : th;
       if (best != ~0ull) {
         const float kd = key_dist(best);
-        const float tv = M == kL2 ? fminf(a.t_init, scan_sq_bound(kd)) : fminf(a.t_init, kd);
-        H[tid] = fmaxf(H[tid], HB[tid] - a.scale * tv);
+        if constexpr (kIsDotFamily<M>) {
+          H[tid] = fmaxf(H[tid], scan_dot_h(fin, HB[tid], fminf(a.t_init, kd)));
+        } else {
+          const float tv = M == kL2 ? fminf(a.t_init, scan_sq_bound(kd)) : fminf(a.t_init, kd);
+          H[tid] = fmaxf(H[tid], HB[tid] - a.scale * tv);
+        }
       }
     }
     if (a.stats && tid == 0) atomicAdd(&a.stats[1], 1ull);
@@ -317,7 +326,9 @@ ngt_scan_mfma_wide_kernel(MfmaScanArgs a) {
       for (int nt = 0; nt < 2; nt++) {
         const int q = ql0 + nt * 32;
         if (pv[nt] && q0 + q < a.nq) {
-          const float hb = float_of_ord(pv[nt]) - HM[q];
+          float hb;
+          if constexpr (kIsDotFamily<M>) hb = scan_dot_boot(fin, HB[q], HM[q], float_of_ord(pv[nt]));
+          else hb = float_of_ord(pv[nt]) - HM[q];
           if (hb > H[q]) H[q] = hb;
         }
       }
@@ -453,6 +464,9 @@ hipError_t launch_scan_mfma_wide(const MfmaScanArgs& a, int metric, int passes, 
   else if (metric == kL2 && passes == 1) launch_scan_mfma_wide_t<kL2, 1>(a, grid, s);
   else if (metric == kCosine && passes == 3) launch_scan_mfma_wide_t<kCosine, 3>(a, grid, s);
   else if (metric == kCosine && passes == 1) launch_scan_mfma_wide_t<kCosine, 1>(a, grid, s);
+  else if (metric == kAngle && passes == 3) launch_scan_mfma_wide_t<kAngle, 3>(a, grid, s);
+  else if ((metric == kNormalizedAngle || metric == kNormalizedCosine || metric == kNormalizedL2) && passes == 3)
+    launch_scan_mfma_wide_t<kScanDot, 3>(a, grid, s);
   else return hipErrorNotSupported;
   return hipGetLastError();
 }
