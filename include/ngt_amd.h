@@ -219,7 +219,9 @@ int ngt_amd_last_search_filtered(const ngt_amd_index *index);
  * 4 uint8 L1 / Hamming on packed byte-SAD and popcount (batches of >= 32
  * queries, k <= 16, padded dimension <= 256), 5 the bf16 matrix-core filter
  * with lists of 17 .. 128 results (the same float metrics, batches of >= 32
- * queries).  The last call on the index wins. */
+ * queries), 6 float L1 on a byte-SAD filter with exact recompute (batches of
+ * >= 32 queries, k <= 16, padded dimension <= 256).  The last call on the
+ * index wins. */
 int ngt_amd_last_scan_kernel(const ngt_amd_index *index);
 /* The device error word of the launch context of `stream` (created on first
  * use, zeroed on that stream and waited for), read on that stream: the word a

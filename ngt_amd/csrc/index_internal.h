@@ -159,6 +159,8 @@ struct SearchCtx {
   DevBuf<float> shb;             // matrix-core scan: per-query filter base
   DevBuf<uint64_t> gthr;         // matrix-core scan: per-query k-th key shared by the parts
   DevBuf<uint32_t> bq;           // uint8 L1 / Hamming scan: zero-padded queries
+  DevBuf<uint32_t> lq, ltt;      // float L1 scan: the queries' codes and initial thresholds
+  DevBuf<float> leq;             // float L1 scan: the queries' error bounds
   DevBuf<uint32_t> ivf_cid, ivf_cn;  // NGTQ: global-codebook search results [nq][cbs], [nq]
   DevBuf<float> ivf_cd;
   DevBuf<int> err;               // device error flag of the launches on this stream
@@ -257,6 +259,11 @@ struct ngt_amd_index {
     int passes = 0;
     DevBuf<int32_t> u8_nx;       // uint8 L2 scan (scan_u8.hip): the rows' norm column
     uint64_t u8_version = ~0ull;
+    DevBuf<uint32_t> l1f_codes;  // float L1 scan (scan_l1f.hip): the rows' one-byte codes, whole 64-row tiles
+    DevBuf<int32_t> l1f_bias;    // ... and their biases
+    DevBuf<uint32_t> l1f_mm;     // ... the ordered words of the finite minimum and maximum
+    double l1f_lo = 0.0, l1f_s = 1.0;  // the quantiser of this version of the rows
+    uint64_t l1f_version = ~0ull;
   } scan;
   std::atomic<int> last_scan{0};  // the kernel of the latest exact scan (ngt_amd_last_scan_kernel)
   struct {                       // 1-byte filter copy of L2 float rows (filter_kernels.hip)

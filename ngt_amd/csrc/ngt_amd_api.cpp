@@ -23,6 +23,7 @@
 #include "index_internal.h"
 #include "ngt_kernels.h"
 #include "prep_kernels.h"
+#include "scan_l1f_bound.h"
 #include "scan_u8_bound.h"
 #include "session_graph.h"
 
@@ -1280,6 +1281,133 @@ static int linear_search_bytes(ngt_amd_index* ix, SearchCtx* c, LinearArgs& a, h
   return 0;
 }
 
+// The rows' one-byte codes and biases of the float L1 scan (scan_l1f.hip),
+// built once per version of the rows: the finite range on the device, the
+// quantiser of it on the host (scan_l1f_bound.h), then the encode kernel.
+static int ensure_scan_l1f_rows(ngt_amd_index* ix, hipStream_t s) {
+  std::lock_guard<std::mutex> lk(ix->mu);
+  if (ix->scan.l1f_version == ix->rows_version) return 0;
+  const uint64_t npad = (ix->nrows + 63) / 64 * 64;  // 64-row scan tiles
+  const size_t qwords = (size_t)scan_bytes_chunks((int)ix->dp) * 4;
+  HIP_OK(ix->scan.l1f_codes.alloc(npad * qwords));
+  HIP_OK(ix->scan.l1f_bias.alloc(npad));
+  HIP_OK(ix->scan.l1f_mm.alloc(2));
+  const uint32_t init[2] = {~0u, 0u};
+  uint32_t mm[2];
+  HIP_OK(hipMemcpyAsync(ix->scan.l1f_mm.p, init, sizeof(init), hipMemcpyHostToDevice, s));
+  HIP_OK(launch_scan_l1f_range(ix->rows.p, ix->row_bytes, ix->nrows, ix->valid.p, (int)ix->dim, ix->scan.l1f_mm.p, s));
+  HIP_OK(hipMemcpyAsync(mm, ix->scan.l1f_mm.p, sizeof(mm), hipMemcpyDeviceToHost, s));
+  HIP_OK(hipStreamSynchronize(s));
+  const L1fQuant z = l1f_quant(scan_l1f_range_value(mm[0]), scan_l1f_range_value(mm[1]), mm[0] <= mm[1]);
+  L1fEncodeArgs e{};
+  e.src = ix->rows.p;
+  e.stride = ix->row_bytes;
+  e.n = ix->nrows;
+  e.n_pad = npad;
+  e.valid = ix->valid.p;
+  e.dim = (int)ix->dim;
+  e.dp = (int)ix->dp;
+  e.lo = z.lo;
+  e.s = z.s;
+  e.codes = ix->scan.l1f_codes.p;
+  e.bias = ix->scan.l1f_bias.p;
+  HIP_OK(launch_scan_l1f_encode(e, false, s));
+  // other streams may scan as soon as the version is published
+  HIP_OK(hipStreamSynchronize(s));
+  ix->scan.l1f_lo = z.lo;
+  ix->scan.l1f_s = z.s;
+  ix->scan.l1f_version = ix->rows_version;
+  return 0;
+}
+
+// float L1 batches: a wave per 128 queries x one part of the rows, lane = row,
+// a byte-SAD filter with a proven bound and the comparator's own arithmetic
+// for what it cannot reject (scan_l1f.hip).
+static int linear_search_l1f(ngt_amd_index* ix, SearchCtx* c, LinearArgs& a, hipStream_t s) {
+  if (ensure_scan_l1f_rows(ix, s)) return -1;
+  const uint32_t mblocks = (a.nq + 127) / 128;  // 128 queries per wave
+  const uint32_t ntiles = (uint32_t)((ix->nrows + 63) / 64);
+  // One resident set of waves over every query block, as for the bytes scan:
+  // four waves per SIMD hide each other's scalar loads where the kernel's
+  // VGPRs allow them (up to 128: Dp <= 128), two beyond (Dp <= 256 takes 175),
+  // fewer where the k-lists (128 k 8 + 256 bytes a wave) fill the CU's LDS first
+  uint32_t wpc = std::min<uint32_t>(ix->dp > 128 ? 8 : 16, (uint32_t)(ix->lds_per_cu / (128 * a.k * 8 + 256)));
+  wpc = std::max<uint32_t>(4, wpc / 4 * 4);
+  uint32_t np = std::max<uint32_t>(1, (uint32_t)ix->cu_count * wpc / mblocks);
+  // for tests: at most this many parts, so that a small table still has parts of several tiles
+  if (const char* v = ngt_amd::knob("NGT_AMD_SCAN_L1F_PARTS"))
+    if (atoi(v) > 0) np = std::min(np, (uint32_t)atoi(v));
+  np = std::min(np, ntiles);
+  const uint32_t per = (ntiles + np - 1) / np;
+  const size_t qwords = (size_t)scan_bytes_chunks((int)ix->dp) * 4;
+  const uint64_t nqpad = (uint64_t)mblocks * 128;
+  HIP_OK(c->lq.alloc(nqpad * qwords));
+  HIP_OK(c->leq.alloc(nqpad));
+  HIP_OK(c->ltt.alloc(nqpad));
+  L1fEncodeArgs e{};
+  e.src = a.queries;
+  e.stride = a.query_bytes;
+  e.n = a.nq;
+  e.n_pad = nqpad;
+  e.dim = (int)ix->dim;
+  e.dp = (int)ix->dp;
+  e.lo = ix->scan.l1f_lo;
+  e.s = ix->scan.l1f_s;
+  e.codes = c->lq.p;
+  e.eq = c->leq.p;
+  e.tt0 = c->ltt.p;
+  // a finite radius as the first k-th distance (rounded up: the exact rule is
+  // the kernel's); a NaN radius accepts nothing there, whatever the filter passes
+  e.kd_init = INFINITY;
+  if (a.radius >= 0.0 && a.radius < 3.0e38) {
+    e.kd_init = (float)a.radius;
+    if ((double)e.kd_init < a.radius) e.kd_init = std::nextafterf(e.kd_init, INFINITY);
+  }
+  HIP_OK(launch_scan_l1f_encode(e, true, s));
+  L1fScanArgs m{};
+  m.codes = ix->scan.l1f_codes.p;
+  m.bias = ix->scan.l1f_bias.p;
+  m.rows = ix->rows.p;
+  m.row_bytes = ix->row_bytes;
+  m.qcodes = c->lq.p;
+  m.eq = c->leq.p;
+  m.tt0 = c->ltt.p;
+  m.queries = a.queries;
+  m.query_bytes = a.query_bytes;
+  m.nq = a.nq;
+  m.k = a.k;
+  m.dp = (int)ix->dp;
+  m.lo = ix->scan.l1f_lo;
+  m.s = ix->scan.l1f_s;
+  m.mblocks = mblocks;
+  m.ntiles = ntiles;
+  m.tiles_per_part = per;
+  m.nparts = (ntiles + per - 1) / per;
+  m.radius = a.radius;
+  static const bool stats = ngt_amd::knob("NGT_AMD_SCAN_STATS") != nullptr;
+  static DevBuf<unsigned long long> d_stats;
+  if (stats) {
+    HIP_OK(d_stats.alloc(2));
+    HIP_OK(hipMemsetAsync(d_stats.p, 0, 2 * sizeof(unsigned long long), s));
+    m.stats = d_stats.p;
+  }
+  HIP_OK(c->partial.alloc((size_t)a.nq * m.nparts * a.k));
+  m.partial = c->partial.p;
+  HIP_OK(launch_scan_l1f(m, s));
+  a.partial = m.partial;
+  HIP_OK(launch_linear_merge(a, m.nparts, s));
+  // all-NaN queries: the ids in the order linearSearch's heap leaves them (with a radius none passes)
+  if (a.radius < 0.0) HIP_OK(launch_scan_l1f_nan(m, a.out_ids, a.out_stride, s));
+  if (stats) {
+    unsigned long long h[2];
+    HIP_OK(hipMemcpyAsync(h, d_stats.p, sizeof(h), hipMemcpyDeviceToHost, s));
+    HIP_OK(hipStreamSynchronize(s));
+    fprintf(stderr, "scan_l1f: nq %u parts %u rows_per_part %u candidates %llu (%.2f per query and part) tile_queries %llu\n",
+            a.nq, m.nparts, per * 64, h[0], (double)h[0] / ((double)a.nq * m.nparts), h[1]);
+  }
+  return 0;
+}
+
 extern "C" int ngt_amd_last_scan_kernel(const ngt_amd_index* ix) { return ix ? ix->last_scan.load() : 0; }
 
 extern "C" int ngt_amd_linear_search_device(ngt_amd_index* ix, const void* d_queries, uint64_t query_bytes,
@@ -1359,6 +1487,18 @@ extern "C" int ngt_amd_linear_search_device(ngt_amd_index* ix, const void* d_que
       ix->nrows > 1) {
     ix->last_scan = 4;
     return linear_search_bytes(ix, c, a, s);
+  }
+  // Batches of queries, float L1: a byte-SAD filter over one-byte codes of
+  // rows and queries with a proven bound, the comparator's own arithmetic for
+  // the pairs it cannot reject (scan_l1f.hip); k <= 16 is the length of its
+  // LDS lists, Dp <= 256 the code row a lane keeps in registers twice over.
+  // Float rows and queries are read 16 bytes at a time.  The knob is read per call.
+  const char* l1f_knob = ngt_amd::knob("NGT_AMD_LINEAR_L1F");
+  if (!(l1f_knob && atoi(l1f_knob) == 0) && nq >= 32 && ix->otype == NGT_AMD_OBJECT_FLOAT &&
+      ix->metric == NGT_AMD_DISTANCE_L1 && k <= 16 && ix->dp <= 256 && ix->dp % 16 == 0 && ix->dim <= ix->dp &&
+      ix->row_bytes % 16 == 0 && query_bytes % 16 == 0 && (uintptr_t)d_queries % 16 == 0 && ix->nrows > 1) {
+    ix->last_scan = 6;
+    return linear_search_l1f(ix, c, a, s);
   }
   // Batches of queries: the query-tiled scan (128 queries per workgroup,
   // packed FMA, scan_kernels.hip) over enough row parts for ~3 workgroups

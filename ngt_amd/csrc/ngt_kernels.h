@@ -458,6 +458,51 @@ hipError_t launch_scan_bytes_prep(const uint8_t* queries, uint64_t query_bytes, 
                                   uint32_t mblocks, hipStream_t s);
 hipError_t launch_scan_bytes(const BytesScanArgs& a, int metric, hipStream_t s);
 
+// float L1 exact scan on a byte-SAD filter with exact recompute (scan_l1f.hip,
+// the rules: scan_l1f_bound.h): Dp <= 256, k <= 16, float rows and query rows
+// 16-byte aligned.
+struct L1fEncodeArgs {
+  const uint8_t* src;            // float rows / prepared queries, stride bytes apart
+  uint64_t stride;
+  uint64_t n;                    // vectors in src
+  uint64_t n_pad;                // code rows to write (>= n; the rest zero)
+  const uint8_t* valid;          // rows: [n] or null
+  int dim, dp;                   // columns coded (the real dimension) and compared
+  double lo, s;                  // the quantiser (L1fQuant)
+  uint32_t* codes;               // [n_pad][4 * scan_bytes_chunks(dp)]
+  int32_t* bias;                 // rows: [n_pad] kL1fEmax - E_x, 0 forced, kL1fNever removed / dummy / padding
+  float* eq;                     // queries: [n_pad] e_q rounded up (+inf: a non-finite element)
+  uint32_t* tt0;                 // queries: [n_pad] T(radius, e_q) + kL1fEmax
+  float kd_init;                 // queries: the radius as a k-th distance, +inf without one
+};
+struct L1fScanArgs {
+  const uint32_t* codes;         // [ntiles * 64][4 * NC] the rows' codes
+  const int32_t* bias;           // [ntiles * 64]
+  const uint8_t* rows;           // the float rows
+  uint64_t row_bytes;
+  const uint32_t* qcodes;        // [mblocks * 128][4 * NC], read-only during the scan
+  const float* eq;               // [mblocks * 128]
+  const uint32_t* tt0;           // [mblocks * 128]
+  const uint8_t* queries;        // the prepared float queries, read-only during the scan
+  uint64_t query_bytes;
+  uint32_t nq, k;
+  int dp;
+  double lo, s;
+  uint32_t mblocks, ntiles, tiles_per_part, nparts;  // 64-row tiles
+  double radius;
+  unsigned long long* stats;     // or null: [0] pairs recomputed, [1] (tile, query) with survivors
+  uint64_t* partial;             // [nq][nparts][k]
+};
+// the finite minimum and maximum of the valid rows' first dim columns, as
+// ordered words: mm[0] min (all ones at launch), mm[1] max (zero at launch)
+hipError_t launch_scan_l1f_range(const uint8_t* rows, uint64_t row_bytes, uint64_t nrows, const uint8_t* valid,
+                                 int dim, uint32_t* mm, hipStream_t s);
+hipError_t launch_scan_l1f_encode(const L1fEncodeArgs& a, bool query, hipStream_t s);
+hipError_t launch_scan_l1f(const L1fScanArgs& a, hipStream_t s);
+// after the merge, without a radius: the ids of queries with a NaN element in linearSearch's order
+hipError_t launch_scan_l1f_nan(const L1fScanArgs& a, uint32_t* out_ids, uint32_t out_stride, hipStream_t s);
+float scan_l1f_range_value(uint32_t ordered);  // the float of an ordered word of launch_scan_l1f_range
+
 // ---- NGTQG (qg_kernels.hip) ------------------------------------------------
 struct QgLutArgs {
   const uint8_t* queries;        // prepared float query rows (padded dp)

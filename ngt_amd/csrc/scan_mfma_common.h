@@ -53,12 +53,33 @@ __device__ __forceinline__ float fold16_lane(const float* v) {
   for (int j = 0; j < 4; j++) t4[j] = t8[j + 4] + t8[j];
   return (t4[0] + t4[1]) + (t4[2] + t4[3]);
 }
+// compareL1 on one lane, bit for bit dist_f32<kL1>: the 8 AVX accumulator
+// lanes as 8 registers, lane j taking columns 8i + j in column order, the
+// fold ((l0+l1)+(l2+l3))+((l4+l5)+(l6+l7)).  QP: the query through any pointer
+// to float (scan_l1f.hip reads it through the scalar cache).
+template <typename QP>
+__device__ __forceinline__ float dist_lane_l1(QP q, const float* __restrict__ x, int dp) {
+  const float4* x4 = reinterpret_cast<const float4*>(x);
+  float l[8];
+#pragma unroll
+  for (int j = 0; j < 8; j++) l[j] = 0.0f;
+#pragma unroll 2
+  for (int i = 0; i < (dp >> 3); i++) {
+    const float4 a = x4[2 * i], b = x4[2 * i + 1];
+    const float xa[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+#pragma unroll
+    for (int j = 0; j < 8; j++) l[j] = l[j] + __builtin_fabsf(q[8 * i + j] - xa[j]);
+  }
+  return ((l[0] + l[1]) + (l[2] + l[3])) + ((l[4] + l[5]) + (l[6] + l[7]));
+}
 template <int M>
 __device__ __forceinline__ float dist_lane(const float* __restrict__ q, const float* __restrict__ x, int dp,
                                            int fin = 0) {
   const float4* q4 = reinterpret_cast<const float4*>(q);
   const float4* x4 = reinterpret_cast<const float4*>(x);
-  if constexpr (M == kL2) {
+  if constexpr (M == kL1) {
+    return dist_lane_l1(q, x, dp);
+  } else if constexpr (M == kL2) {
     float acc[16];
 #pragma unroll
     for (int l = 0; l < 16; l++) acc[l] = 0.0f;

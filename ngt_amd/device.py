@@ -218,7 +218,8 @@ class DeviceIndex(object):
         """Kernel of the latest linear search on the index: 0 quad-per-row,
         1 tiled FMA, 2 bf16 matrix-core filter, 3 uint8 L2 on the int8 matrix cores,
         4 uint8 L1 / Hamming on packed byte-SAD and popcount, 5 the bf16
-        matrix-core filter with lists of 17 .. 128 results."""
+        matrix-core filter with lists of 17 .. 128 results, 6 float L1 on a
+        byte-SAD filter with exact recompute."""
         return int(self.L.ngt_amd_last_scan_kernel(self.h))
 
     def last_search_lookahead(self):
