@@ -259,6 +259,10 @@ struct ngt_amd_index {
     int passes = 0;
     DevBuf<int32_t> u8_nx;       // uint8 L2 scan (scan_u8.hip): the rows' norm column
     uint64_t u8_version = ~0ull;
+    DevBuf<int32_t> u8c_cx;      // uint8 Cosine / Angle scan (scan_u8cos.hip): the rows' correction column,
+    DevBuf<uint32_t> u8c_nb;     // ... their |x|^2
+    DevBuf<float> u8c_rx;        // ... and the filter's sqrt of it (NaN: removed, dummy, padding)
+    uint64_t u8c_version = ~0ull;
     DevBuf<uint32_t> l1f_codes;  // float L1 scan (scan_l1f.hip): the rows' one-byte codes, whole 64-row tiles
     DevBuf<int32_t> l1f_bias;    // ... and their biases
     DevBuf<uint32_t> l1f_mm;     // ... the ordered words of the finite minimum and maximum

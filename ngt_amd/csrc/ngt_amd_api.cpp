@@ -1237,6 +1237,70 @@ static int linear_search_u8(ngt_amd_index* ix, SearchCtx* c, LinearArgs& a, hipS
   return 0;
 }
 
+// The rows' state of the uint8 Cosine / Angle scan (scan_u8cos.hip): the
+// correction column, |x|^2 and its float root, built once per version of the rows.
+static int ensure_scan_u8cos_rows(ngt_amd_index* ix, hipStream_t s) {
+  std::lock_guard<std::mutex> lk(ix->mu);
+  if (ix->scan.u8c_version == ix->rows_version) return 0;
+  const uint64_t npad = (ix->nrows + 255) / 256 * 256;  // 256-row scan tiles
+  HIP_OK(ix->scan.u8c_cx.alloc(npad));
+  HIP_OK(ix->scan.u8c_nb.alloc(npad));
+  HIP_OK(ix->scan.u8c_rx.alloc(npad));
+  HIP_OK(launch_scan_u8cos_rows(ix->rows.p, ix->row_bytes, ix->nrows, ix->valid.p, (int)ix->dp, ix->scan.u8c_cx.p,
+                                ix->scan.u8c_nb.p, ix->scan.u8c_rx.p, npad, s));
+  // other streams may scan as soon as the version is published
+  HIP_OK(hipStreamSynchronize(s));
+  ix->scan.u8c_version = ix->rows_version;
+  return 0;
+}
+
+// uint8 Cosine / Angle batches: exact integer dot products from the int8
+// matrix cores, survivors finished from (s, na, nb) alone (scan_u8cos.hip);
+// the kernel sorts its per-part lists in place in `partial`, merged like every
+// other scan's.  pend: the pending slots per query that fit beside the queries.
+static int linear_search_u8cos(ngt_amd_index* ix, SearchCtx* c, LinearArgs& a, uint32_t pend, hipStream_t s) {
+  if (ensure_scan_u8cos_rows(ix, s)) return -1;
+  const uint32_t mblocks = (a.nq + 127) / 128;  // 128 queries per workgroup
+  const uint32_t ntiles = (uint32_t)((ix->nrows + 255) / 256);
+  // one workgroup per CU: every query block x floor(CUs / blocks) parts
+  uint32_t np = std::max<uint32_t>(1, (uint32_t)ix->cu_count / mblocks);
+  np = std::min(np, ntiles);
+  const uint32_t per = (ntiles + np - 1) / np;
+  U8CosScanArgs m{};
+  m.rows = ix->rows.p;
+  m.row_bytes = ix->row_bytes;
+  m.nrows = ix->nrows;
+  m.cx = ix->scan.u8c_cx.p;
+  m.nb = ix->scan.u8c_nb.p;
+  m.rx = ix->scan.u8c_rx.p;
+  m.queries = a.queries;
+  m.query_bytes = a.query_bytes;
+  m.nq = a.nq;
+  m.k = a.k;
+  m.dp = (int)ix->dp;
+  m.pend = pend;
+  m.mblocks = mblocks;
+  m.ntiles = ntiles;
+  m.tiles_per_part = per;
+  m.nparts = (ntiles + per - 1) / per;
+  m.radius = a.radius;
+  // a finite radius as the first k-th distance (rounded up: the exact rule is
+  // the kernel's); a NaN radius bounds nothing and accepts nothing there
+  m.kd_init = INFINITY;
+  if (a.radius >= 0.0 && a.radius < 3.0e38) {
+    m.kd_init = (float)a.radius;
+    if ((double)m.kd_init < a.radius) m.kd_init = std::nextafterf(m.kd_init, INFINITY);
+  }
+  HIP_OK(c->partial.alloc((size_t)a.nq * m.nparts * a.k));
+  m.partial = c->partial.p;
+  const hipError_t e = launch_scan_u8cos(m, ix->metric, s);
+  if (e == hipErrorNotSupported) return 1;  // the caller falls through to the quad kernel
+  HIP_OK(e);
+  a.partial = m.partial;
+  HIP_OK(launch_linear_merge(a, m.nparts, s));
+  return 0;
+}
+
 // uint8 L1 / Hamming batches: a wave per 128 queries x one part of the rows,
 // lane = row, exact integer sums by v_sad_u8 / v_bcnt (scan_bytes.hip).
 static int linear_search_bytes(ngt_amd_index* ix, SearchCtx* c, LinearArgs& a, hipStream_t s) {
@@ -1475,6 +1539,22 @@ extern "C" int ngt_amd_linear_search_device(ngt_amd_index* ix, const void* d_que
       (uintptr_t)d_queries % 16 == 0 && ix->row_bytes % 16 == 0) {
     ix->last_scan = 3;
     return linear_search_u8(ix, c, a, s);
+  }
+  // Batches of queries, uint8 Cosine / Angle: exact integer dot products on
+  // the int8 matrix cores, distances finished from the integers
+  // (scan_u8cos.hip); lists of up to 128 results sorted in place in the
+  // partial buffer.  A row that leaves no LDS for the pending slots falls
+  // through to the quad kernel.  The knob is read per call.
+  const char* u8cos_knob = ngt_amd::knob("NGT_AMD_LINEAR_U8COS");
+  if (!(u8cos_knob && atoi(u8cos_knob) == 0) && nq >= 32 && ix->otype == NGT_AMD_OBJECT_UINT8 &&
+      (ix->metric == NGT_AMD_DISTANCE_COSINE || ix->metric == NGT_AMD_DISTANCE_ANGLE) && k <= 128 && ix->dp <= 1024 &&
+      ix->dp % 16 == 0 && query_bytes % 16 == 0 && (uintptr_t)d_queries % 16 == 0 && ix->row_bytes % 16 == 0 &&
+      ix->nrows > 1 && scan_u8cos_pend((int)ix->dp) != 0) {
+    const int rc = linear_search_u8cos(ix, c, a, scan_u8cos_pend((int)ix->dp), s);
+    if (rc <= 0) {
+      if (rc == 0) ix->last_scan = 7;
+      return rc;
+    }
   }
   // Batches of queries, uint8 L1 / Hamming: exact integer sums by packed
   // byte-SAD and popcount (scan_bytes.hip); k <= 16 is the length of its LDS

@@ -439,6 +439,34 @@ hipError_t launch_scan_u8_norms(const uint8_t* rows, uint64_t row_bytes, uint64_
 hipError_t launch_scan_u8(const U8ScanArgs& a, hipStream_t s);
 size_t scan_u8_lds_bytes(uint32_t k, int dp, uint32_t pend);
 
+// uint8 Cosine / Angle exact scan on the int8 matrix cores (scan_u8cos.hip,
+// the rules: scan_u8cos_bound.h): Dp <= 1024 a multiple of 16, 1 <= k <= 128,
+// query rows 16-byte aligned.  The (query, part) lists are sorted in place in
+// a.partial, the LDS does not grow with k.
+struct U8CosScanArgs {
+  const uint8_t* rows;
+  uint64_t row_bytes;
+  uint64_t nrows;                // > 1
+  const int32_t* cx;             // [ntiles * 256] the row's term of s: 128 sum x
+  const uint32_t* nb;            // [ntiles * 256] |x|^2
+  const float* rx;               // [ntiles * 256] (float)sqrt(nb); NaN for removed, dummy and padding rows
+  const uint8_t* queries;
+  uint64_t query_bytes;
+  uint32_t nq, k;
+  int dp;
+  uint32_t pend;                 // pending slots per query: scan_u8cos_pend(dp)
+  uint32_t mblocks, ntiles, tiles_per_part, nparts;
+  double radius;
+  float kd_init;                 // the radius as a k-th distance (not below it), +inf without one
+  uint64_t* partial;             // [nq][nparts][k]
+};
+hipError_t launch_scan_u8cos_rows(const uint8_t* rows, uint64_t row_bytes, uint64_t nrows, const uint8_t* valid, int dp,
+                                  int32_t* cx, uint32_t* nb, float* rx, uint64_t npad, hipStream_t s);
+// metric: Cosine or Angle; hipErrorNotSupported where the LDS does not hold the queries and a.pend slots
+hipError_t launch_scan_u8cos(const U8CosScanArgs& a, int metric, hipStream_t s);
+size_t scan_u8cos_lds_bytes(int dp, uint32_t pend);
+uint32_t scan_u8cos_pend(int dp);  // 64, 32 or 16 pending slots per query, 0 where none fits
+
 // uint8 L1 / Hamming exact scan on packed byte-SAD and popcount
 // (scan_bytes.hip): Dp <= 256 a multiple of 16, k <= 16, rows 16-byte aligned.
 struct BytesScanArgs {

@@ -219,7 +219,8 @@ class DeviceIndex(object):
         1 tiled FMA, 2 bf16 matrix-core filter, 3 uint8 L2 on the int8 matrix cores,
         4 uint8 L1 / Hamming on packed byte-SAD and popcount, 5 the bf16
         matrix-core filter with lists of 17 .. 128 results, 6 float L1 on a
-        byte-SAD filter with exact recompute."""
+        byte-SAD filter with exact recompute, 7 uint8 Cosine / Angle on the
+        int8 matrix cores."""
         return int(self.L.ngt_amd_last_scan_kernel(self.h))
 
     def last_search_lookahead(self):
