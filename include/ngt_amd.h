@@ -222,7 +222,9 @@ int ngt_amd_last_search_filtered(const ngt_amd_index *index);
  * queries), 6 float L1 on a byte-SAD filter with exact recompute (batches of
  * >= 32 queries, k <= 16, padded dimension <= 256), 7 uint8 Cosine / Angle
  * on the int8 matrix cores (batches of >= 32 queries, k <= 128, padded
- * dimension <= 1024).  The last call on the index wins. */
+ * dimension <= 1024), 8 uint8 L2 on the int8 matrix cores with lists of
+ * 17 .. 128 results (batches of >= 32 queries, padded dimension <= 1024;
+ * opt-in for now).  The last call on the index wins. */
 int ngt_amd_last_scan_kernel(const ngt_amd_index *index);
 /* The device error word of the launch context of `stream` (created on first
  * use, zeroed on that stream and waited for), read on that stream: the word a

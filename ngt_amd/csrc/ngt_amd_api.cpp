@@ -1197,15 +1197,14 @@ static int ensure_scan_u8_rows(ngt_amd_index* ix, hipStream_t s) {
   return 0;
 }
 
-// uint8 L2 batches: exact integer sums from the int8 matrix cores
-// (scan_u8.hip), per-part lists merged like every other scan's.
-static int linear_search_u8(ngt_amd_index* ix, SearchCtx* c, LinearArgs& a, hipStream_t s) {
-  if (ensure_scan_u8_rows(ix, s)) return -1;
+// What the two uint8 L2 matrix-core scans share: the parts (one workgroup per
+// CU: every query block x floor(CUs / blocks) parts, parts_cap at the most)
+// and the threshold of the radius.  pend and partial are the caller's.
+static U8ScanArgs scan_u8_args(const ngt_amd_index* ix, const LinearArgs& a, uint32_t parts_cap) {
   const uint32_t mblocks = (a.nq + 127) / 128;  // 128 queries per workgroup
   const uint32_t ntiles = (uint32_t)((ix->nrows + 255) / 256);
-  // one workgroup per CU: every query block x floor(CUs / blocks) parts
   uint32_t np = std::max<uint32_t>(1, (uint32_t)ix->cu_count / mblocks);
-  np = std::min(np, ntiles);
+  np = std::min(std::min(np, ntiles), parts_cap);
   const uint32_t per = (ntiles + np - 1) / np;
   U8ScanArgs m{};
   m.rows = ix->rows.p;
@@ -1217,7 +1216,6 @@ static int linear_search_u8(ngt_amd_index* ix, SearchCtx* c, LinearArgs& a, hipS
   m.nq = a.nq;
   m.k = a.k;
   m.dp = (int)ix->dp;
-  m.pend = scan_u8_lds_bytes(a.k, m.dp, 16) <= 160 * 1024 ? 16 : 8;
   m.mblocks = mblocks;
   m.ntiles = ntiles;
   m.tiles_per_part = per;
@@ -1229,9 +1227,40 @@ static int linear_search_u8(ngt_amd_index* ix, SearchCtx* c, LinearArgs& a, hipS
     if ((double)d < a.radius) d = u8_next_up(d);
     m.s_init = u8_sum_threshold(d);
   }
+  return m;
+}
+
+// uint8 L2 batches: exact integer sums from the int8 matrix cores
+// (scan_u8.hip), per-part lists merged like every other scan's.
+static int linear_search_u8(ngt_amd_index* ix, SearchCtx* c, LinearArgs& a, hipStream_t s) {
+  if (ensure_scan_u8_rows(ix, s)) return -1;
+  U8ScanArgs m = scan_u8_args(ix, a, UINT32_MAX);
+  m.pend = scan_u8_lds_bytes(a.k, m.dp, 16) <= 160 * 1024 ? 16 : 8;
   HIP_OK(c->partial.alloc((size_t)a.nq * m.nparts * a.k));
   m.partial = c->partial.p;
   HIP_OK(launch_scan_u8(m, s));
+  a.partial = m.partial;
+  HIP_OK(launch_linear_merge(a, m.nparts, s));
+  return 0;
+}
+
+// uint8 L2 batches with lists of 17 .. 128 results: the same sums and norm
+// column, the per-part lists sorted in place in `partial` by the kernel
+// (scan_u8_wide.hip).  NGT_AMD_SCAN_WIDE_PARTS caps the parts here too, so
+// that a test's small table still has parts of several tiles.  1: the
+// launcher refused the shape, the caller falls through to the quad kernel.
+static int linear_search_u8_wide(ngt_amd_index* ix, SearchCtx* c, LinearArgs& a, hipStream_t s) {
+  if (ensure_scan_u8_rows(ix, s)) return -1;
+  uint32_t parts_cap = UINT32_MAX;
+  if (const char* v = ngt_amd::knob("NGT_AMD_SCAN_WIDE_PARTS"))
+    if (atoi(v) > 0) parts_cap = (uint32_t)atoi(v);
+  U8ScanArgs m = scan_u8_args(ix, a, parts_cap);
+  m.pend = scan_u8_wide_pend(m.dp);
+  HIP_OK(c->partial.alloc((size_t)a.nq * m.nparts * a.k));
+  m.partial = c->partial.p;
+  const hipError_t e = launch_scan_u8_wide(m, s);
+  if (e == hipErrorNotSupported) return 1;
+  HIP_OK(e);
   a.partial = m.partial;
   HIP_OK(launch_linear_merge(a, m.nparts, s));
   return 0;
@@ -1539,6 +1568,20 @@ extern "C" int ngt_amd_linear_search_device(ngt_amd_index* ix, const void* d_que
       (uintptr_t)d_queries % 16 == 0 && ix->row_bytes % 16 == 0) {
     ix->last_scan = 3;
     return linear_search_u8(ix, c, a, s);
+  }
+  // The same sums with lists of 17 .. 128 results (scan_u8_wide.hip), sorted
+  // in place in the partial buffer.  Opt-in for now: only a non-zero
+  // NGT_AMD_LINEAR_U8WIDE, read per call, takes it; a shape the launcher
+  // refuses falls through to the quad kernel.
+  const char* u8wide_knob = ngt_amd::knob("NGT_AMD_LINEAR_U8WIDE");
+  if (u8wide_knob && atoi(u8wide_knob) != 0 && nq >= 32 && ix->otype == NGT_AMD_OBJECT_UINT8 &&
+      ix->metric == NGT_AMD_DISTANCE_L2 && k >= 17 && k <= 128 && ix->dp <= 1024 && ix->dp % 16 == 0 &&
+      query_bytes % 16 == 0 && (uintptr_t)d_queries % 16 == 0 && ix->row_bytes % 16 == 0) {
+    const int rc = linear_search_u8_wide(ix, c, a, s);
+    if (rc <= 0) {
+      if (rc == 0) ix->last_scan = 8;
+      return rc;
+    }
   }
   // Batches of queries, uint8 Cosine / Angle: exact integer dot products on
   // the int8 matrix cores, distances finished from the integers

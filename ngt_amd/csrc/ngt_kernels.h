@@ -428,7 +428,7 @@ struct U8ScanArgs {
   uint64_t query_bytes;
   uint32_t nq, k;
   int dp;
-  uint32_t pend;                 // pending slots per query (16; 8 where the LDS is short)
+  uint32_t pend;                 // pending slots per query (16; 8 where the LDS is short; wide: scan_u8_wide_pend(dp))
   uint32_t mblocks, ntiles, tiles_per_part, nparts;
   double radius;
   int32_t s_init;                // the threshold of the radius, kU8SumAll without one
@@ -438,6 +438,13 @@ hipError_t launch_scan_u8_norms(const uint8_t* rows, uint64_t row_bytes, uint64_
                                 int32_t* nx, uint64_t npad, hipStream_t s);
 hipError_t launch_scan_u8(const U8ScanArgs& a, hipStream_t s);
 size_t scan_u8_lds_bytes(uint32_t k, int dp, uint32_t pend);
+// The same sums for 17 <= k <= 128 (scan_u8_wide.hip), same arguments and norm
+// column: the (query, part) lists are sorted in place in a.partial, the LDS
+// does not grow with k.  hipErrorNotSupported where the LDS does not hold the
+// queries and a.pend slots.
+hipError_t launch_scan_u8_wide(const U8ScanArgs& a, hipStream_t s);
+size_t scan_u8_wide_lds_bytes(int dp, uint32_t pend);
+uint32_t scan_u8_wide_pend(int dp);  // 64, 32 or 16 pending slots per query, 0 where none fits
 
 // uint8 Cosine / Angle exact scan on the int8 matrix cores (scan_u8cos.hip,
 // the rules: scan_u8cos_bound.h): Dp <= 1024 a multiple of 16, 1 <= k <= 128,

@@ -44,6 +44,7 @@
 #include "ngt_device.h"
 #include "ngt_kernels.h"
 #include "scan_u8_bound.h"
+#include "scan_u8_lane.h"
 
 namespace ngt_amd {
 
@@ -55,29 +56,6 @@ constexpr int kU8R = 256;         // rows per tile
 constexpr int kU8W = kU8R / 32;   // candidate bitmap words per query
 constexpr int kU8Chunk = 128;     // bytes of a row per pipeline stage (4 k-steps)
 constexpr int kU8Shift = (int)0x80808080u;
-
-// The comparator on one lane: PrimitiveComparator's four float lanes (lane c:
-// elements e with e mod 4 == c) as exact integers, the folds and double sqrt
-// of dist_u8<kL2> (ngt_device.h).
-__device__ __forceinline__ float u8_l2_lane(const uint8_t* __restrict__ q, const uint8_t* __restrict__ x, int dp) {
-  const uint32_t* qw = reinterpret_cast<const uint32_t*>(q);
-  const uint32_t* xw = reinterpret_cast<const uint32_t*>(x);
-  int acc[4] = {0, 0, 0, 0};
-  for (int i = 0; i < (dp >> 2); i++) {
-    const uint32_t qv = qw[i], xv = xw[i];
-#pragma unroll
-    for (int c = 0; c < 4; c++) {
-      const int d = (int)((qv >> (8 * c)) & 0xff) - (int)((xv >> (8 * c)) & 0xff);
-      acc[c] += d * d;
-    }
-  }
-  // f0 + f1 of two exact lane sums (< 2^24 each for dp <= 1024) is the exact
-  // integer rounded to nearest even, which is what the conversion of
-  // acc[0] + acc[1] gives: one rounding either way, and no pair of float adds
-  // for the compiler to pack
-  const float f01 = (float)(acc[0] + acc[1]), f23 = (float)(acc[2] + acc[3]);
-  return (float)sqrt((double)(f01 + f23));
-}
 
 // |x'|^2 of every row, kU8SumNever for removed rows and the padding of the
 // last tile: one thread per row.
