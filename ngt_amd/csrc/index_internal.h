@@ -158,7 +158,8 @@ struct SearchCtx {
   DevBuf<uint16_t> sqh, sql;     // matrix-core scan: queries in fragment order
   DevBuf<float> shb;             // matrix-core scan: per-query filter base
   DevBuf<uint64_t> gthr;         // matrix-core scan: per-query k-th key shared by the parts
-  DevBuf<uint32_t> bq;           // uint8 L1 / Hamming scan: zero-padded queries
+  DevBuf<uint32_t> bq;           // uint8 L1 / Hamming / Jaccard scans: zero-padded queries
+  DevBuf<uint32_t> bqp;          // uint8 Jaccard scan: their popcounts
   DevBuf<uint32_t> lq, ltt;      // float L1 scan: the queries' codes and initial thresholds
   DevBuf<float> leq;             // float L1 scan: the queries' error bounds
   DevBuf<uint32_t> ivf_cid, ivf_cn;  // NGTQ: global-codebook search results [nq][cbs], [nq]
@@ -268,6 +269,9 @@ struct ngt_amd_index {
     DevBuf<uint32_t> l1f_mm;     // ... the ordered words of the finite minimum and maximum
     double l1f_lo = 0.0, l1f_s = 1.0;  // the quantiser of this version of the rows
     uint64_t l1f_version = ~0ull;
+    DevBuf<uint32_t> jz_flag;    // uint8 Jaccard scan (scan_bytes_wide.hip): the zero-row kernel's word
+    bool jz_any = false;         // ... some live row of this version of the rows is all zero
+    uint64_t jz_version = ~0ull;
   } scan;
   std::atomic<int> last_scan{0};  // the kernel of the latest exact scan (ngt_amd_last_scan_kernel)
   struct {                       // 1-byte filter copy of L2 float rows (filter_kernels.hip)

@@ -1374,6 +1374,104 @@ static int linear_search_bytes(ngt_amd_index* ix, SearchCtx* c, LinearArgs& a, h
   return 0;
 }
 
+// Whether a live row is all zero, found once per version of the rows: against
+// an all-zero query such a row has de = 0 and the comparator's NaN, which the
+// Jaccard scan of scan_bytes_wide.hip does not rank.  -1: error.
+static int scan_jaccard_zero_row(ngt_amd_index* ix, hipStream_t s) {
+  std::lock_guard<std::mutex> lk(ix->mu);
+  if (ix->scan.jz_version == ix->rows_version) return ix->scan.jz_any ? 1 : 0;
+  HIP_OK(ix->scan.jz_flag.alloc(1));
+  uint32_t flag = 0;
+  HIP_OK(hipMemcpyAsync(ix->scan.jz_flag.p, &flag, sizeof(flag), hipMemcpyHostToDevice, s));
+  HIP_OK(launch_scan_bytes_wide_zero(ix->rows.p, ix->row_bytes, ix->nrows, ix->valid.p, (int)ix->dp,
+                                     ix->scan.jz_flag.p, s));
+  HIP_OK(hipMemcpyAsync(&flag, ix->scan.jz_flag.p, sizeof(flag), hipMemcpyDeviceToHost, s));
+  HIP_OK(hipStreamSynchronize(s));
+  ix->scan.jz_any = flag != 0;
+  ix->scan.jz_version = ix->rows_version;
+  return flag != 0 ? 1 : 0;
+}
+
+// uint8 L1 / Hamming / Jaccard batches with lists of up to 128 results: the
+// work split of linear_search_bytes, the per-part lists sorted in place in
+// `partial` by the kernel (scan_bytes_wide.hip).  NGT_AMD_SCAN_WIDE_PARTS caps
+// the parts here too, so that a test's small table still has parts of several
+// tiles.  1: a Jaccard table with an all-zero live row, or a shape the launcher
+// refused; the caller falls through to the quad kernel.
+static int linear_search_bytes_wide(ngt_amd_index* ix, SearchCtx* c, LinearArgs& a, hipStream_t s) {
+  const bool jaccard = ix->metric == NGT_AMD_DISTANCE_JACCARD;
+  if (jaccard) {
+    const int z = scan_jaccard_zero_row(ix, s);
+    if (z) return z;
+  }
+  const uint32_t mblocks = (a.nq + 127) / 128;  // 128 queries per wave
+  const uint32_t ntiles = (uint32_t)((ix->nrows + 63) / 64);
+  // One resident set of waves over every query block: four waves per SIMD
+  // where the kernel's VGPRs allow them (up to 110: Dp <= 128), three (L1 /
+  // Hamming, 165) or two (Jaccard, 174) with a 256-byte row; a wave's pending
+  // slots (8 KiB, Jaccard 12 KiB) leave the CU's LDS room for 16 and 12 waves
+  const uint32_t by_lds = (uint32_t)(ix->lds_per_cu / (jaccard ? 12288 : 8192));
+  uint32_t wpc = std::min<uint32_t>(ix->dp > 128 ? (jaccard ? 8 : 12) : 16, by_lds);
+  wpc = std::max<uint32_t>(4, wpc / 4 * 4);
+  uint32_t np = std::max<uint32_t>(1, (uint32_t)ix->cu_count * wpc / mblocks);
+  if (const char* v = ngt_amd::knob("NGT_AMD_SCAN_WIDE_PARTS"))
+    if (atoi(v) > 0) np = std::min(np, (uint32_t)atoi(v));
+  // a row's offset in its part takes 16 bits
+  np = std::max(np, (ntiles + kBytesWideMaxTiles - 1) / kBytesWideMaxTiles);
+  np = std::min(np, ntiles);
+  const uint32_t per = (ntiles + np - 1) / np;
+  BytesWideScanArgs m{};
+  m.rows = ix->rows.p;
+  m.row_bytes = ix->row_bytes;
+  m.nrows = ix->nrows;
+  m.valid = ix->valid.p;
+  m.nq = a.nq;
+  m.k = a.k;
+  m.dp = (int)ix->dp;
+  m.mblocks = mblocks;
+  m.ntiles = ntiles;
+  m.tiles_per_part = per;
+  m.nparts = (ntiles + per - 1) / per;
+  m.radius = a.radius;
+  if (jaccard) {
+    // (c_k << 48 | de_k << 32 | id_k): a pair passes with c de_k > c_k de, or
+    // equal and id < id_k.  (0, 1, ~0) passes every pair; a radius r passes
+    // the ratios from floor((1 - r - 1e-6) 2048) / 2048 on, which is below
+    // every ratio whose float distance is within r -- the exact rule is the
+    // kernel's; NaN passes none (c <= 2048 < 2049 de)
+    m.thr_init = (1ull << 32) | 0xffffffffull;
+    if (!(a.radius < 0.0)) {
+      const double rho = 1.0 - a.radius - 1e-6;
+      if (!(a.radius >= 0.0)) m.thr_init = (2049ull << 48) | (1ull << 32) | 0xffffffffull;
+      else if (rho > 0.0) m.thr_init = ((uint64_t)(rho * 2048.0) << 48) | (2048ull << 32) | 0xffffffffull;
+    }
+  } else {
+    // (radius < 0 || (double)d <= radius) of the quad kernel on d = (float)S:
+    // S <= floor(radius), as a bound on the keys (S << 32 | id)
+    m.thr_init = ~0ull;
+    if (!(a.radius < 0.0)) {
+      if (!(a.radius >= 0.0)) m.thr_init = 0;  // NaN: no distance passes
+      else if (a.radius < 4.0e9) m.thr_init = ((uint64_t)a.radius + 1) << 32;
+    }
+  }
+  HIP_OK(c->bq.alloc((size_t)mblocks * 128 * scan_bytes_chunks(m.dp) * 4));
+  HIP_OK(launch_scan_bytes_prep(a.queries, a.query_bytes, a.nq, m.dp, c->bq.p, mblocks, s));
+  m.qpad = c->bq.p;
+  if (jaccard) {
+    HIP_OK(c->bqp.alloc((size_t)mblocks * 128));
+    HIP_OK(launch_scan_bytes_wide_qpop(c->bq.p, m.dp, mblocks, c->bqp.p, s));
+    m.qpop = c->bqp.p;
+  }
+  HIP_OK(c->partial.alloc((size_t)a.nq * m.nparts * a.k));
+  m.partial = c->partial.p;
+  const hipError_t e = launch_scan_bytes_wide(m, ix->metric, s);
+  if (e == hipErrorNotSupported) return 1;
+  HIP_OK(e);
+  a.partial = m.partial;
+  HIP_OK(launch_linear_merge(a, m.nparts, s));
+  return 0;
+}
+
 // The rows' one-byte codes and biases of the float L1 scan (scan_l1f.hip),
 // built once per version of the rows: the finite range on the device, the
 // quantiser of it on the host (scan_l1f_bound.h), then the encode kernel.
@@ -1610,6 +1708,23 @@ extern "C" int ngt_amd_linear_search_device(ngt_amd_index* ix, const void* d_que
       ix->nrows > 1) {
     ix->last_scan = 4;
     return linear_search_bytes(ix, c, a, s);
+  }
+  // The same sums with lists of 17 .. 128 results, and uint8 Jaccard with
+  // lists of 1 .. 128 (scan_bytes_wide.hip), sorted in place in the partial
+  // buffer.  Opt-in for now: only a non-zero NGT_AMD_LINEAR_BYTESWIDE, read
+  // per call, takes it; a Jaccard table with an all-zero live row and a shape
+  // the launcher refuses fall through to the quad kernel.
+  const char* byteswide_knob = ngt_amd::knob("NGT_AMD_LINEAR_BYTESWIDE");
+  if (byteswide_knob && atoi(byteswide_knob) != 0 && nq >= 32 && ix->otype == NGT_AMD_OBJECT_UINT8 &&
+      ((ix->metric == NGT_AMD_DISTANCE_JACCARD && k >= 1) ||
+       ((ix->metric == NGT_AMD_DISTANCE_L1 || ix->metric == NGT_AMD_DISTANCE_HAMMING) && k >= 17)) &&
+      k <= 128 && ix->dp <= 256 && ix->dp % 16 == 0 && ix->row_bytes % 16 == 0 && query_bytes % 4 == 0 &&
+      (uintptr_t)d_queries % 4 == 0 && ix->nrows > 1) {
+    const int rc = linear_search_bytes_wide(ix, c, a, s);
+    if (rc <= 0) {
+      if (rc == 0) ix->last_scan = 9;
+      return rc;
+    }
   }
   // Batches of queries, float L1: a byte-SAD filter over one-byte codes of
   // rows and queries with a proven bound, the comparator's own arithmetic for

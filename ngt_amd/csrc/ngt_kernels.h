@@ -493,6 +493,35 @@ hipError_t launch_scan_bytes_prep(const uint8_t* queries, uint64_t query_bytes, 
                                   uint32_t mblocks, hipStream_t s);
 hipError_t launch_scan_bytes(const BytesScanArgs& a, int metric, hipStream_t s);
 
+// uint8 L1 / Hamming / Jaccard exact scan with lists of 1 .. 128 results
+// (scan_bytes_wide.hip): Dp <= 256 a multiple of 16, rows 16-byte aligned.
+// The (query, part) lists are sorted in place in a.partial, the LDS does not
+// grow with k.  Jaccard: no live row may be all zero (launch_scan_bytes_wide_zero).
+constexpr uint32_t kBytesWideMaxTiles = 1024;  // 64-row tiles of a part: a row's offset in it takes 16 bits
+struct BytesWideScanArgs {
+  const uint8_t* rows;
+  uint64_t row_bytes;
+  uint64_t nrows;                // > 1
+  const uint8_t* valid;          // [nrows] or null
+  const uint32_t* qpad;          // [mblocks * 128][4 * scan_bytes_chunks(dp)] zero-padded queries, read-only
+  const uint32_t* qpop;          // Jaccard: [mblocks * 128] their popcounts, read-only
+  uint32_t nq, k;
+  int dp;
+  uint32_t mblocks, ntiles, tiles_per_part, nparts;  // 64-row tiles, tiles_per_part <= kBytesWideMaxTiles
+  // the filter's start threshold: L1 / Hamming the radius as a (S << 32 | id)
+  // bound, exactly; Jaccard (c_k << 48 | de_k << 32 | id_k) of a ratio not
+  // above any ratio within the radius; without a radius everything passes
+  uint64_t thr_init;
+  double radius;                 // Jaccard: the exact rule of the entries that reach a list
+  uint64_t* partial;             // [nq][nparts][k]
+};
+hipError_t launch_scan_bytes_wide_qpop(const uint32_t* qpad, int dp, uint32_t mblocks, uint32_t* qpop, hipStream_t s);
+// *flag |= 1 (zero at launch) if a live row is all zero
+hipError_t launch_scan_bytes_wide_zero(const uint8_t* rows, uint64_t row_bytes, uint64_t nrows, const uint8_t* valid,
+                                       int dp, uint32_t* flag, hipStream_t s);
+// metric: L1, Hamming or Jaccard; hipErrorNotSupported for a shape outside the above
+hipError_t launch_scan_bytes_wide(const BytesWideScanArgs& a, int metric, hipStream_t s);
+
 // float L1 exact scan on a byte-SAD filter with exact recompute (scan_l1f.hip,
 // the rules: scan_l1f_bound.h): Dp <= 256, k <= 16, float rows and query rows
 // 16-byte aligned.

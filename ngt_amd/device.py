@@ -221,7 +221,8 @@ class DeviceIndex(object):
         matrix-core filter with lists of 17 .. 128 results, 6 float L1 on a
         byte-SAD filter with exact recompute, 7 uint8 Cosine / Angle on the
         int8 matrix cores, 8 uint8 L2 on the int8 matrix cores with lists of
-        17 .. 128 results."""
+        17 .. 128 results, 9 uint8 L1 / Hamming with lists of 17 .. 128 results
+        and uint8 Jaccard with lists of 1 .. 128 on packed byte-SAD and popcount."""
         return int(self.L.ngt_amd_last_scan_kernel(self.h))
 
     def last_search_lookahead(self):
