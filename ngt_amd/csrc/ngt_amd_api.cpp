@@ -1513,8 +1513,10 @@ static int ensure_scan_l1f_rows(ngt_amd_index* ix, hipStream_t s) {
 
 // float L1 batches: a wave per 128 queries x one part of the rows, lane = row,
 // a byte-SAD filter with a proven bound and the comparator's own arithmetic
-// for what it cannot reject (scan_l1f.hip).
-static int linear_search_l1f(ngt_amd_index* ix, SearchCtx* c, LinearArgs& a, hipStream_t s) {
+// for what it cannot reject (scan_l1f.hip).  wide: lists of up to 128
+// results, sorted in place in `partial` by the kernel (scan_l1f_wide.hip);
+// 1: a shape its launcher refused, the caller falls through to the quad kernel.
+static int linear_search_l1f(ngt_amd_index* ix, SearchCtx* c, LinearArgs& a, hipStream_t s, bool wide = false) {
   if (ensure_scan_l1f_rows(ix, s)) return -1;
   const uint32_t mblocks = (a.nq + 127) / 128;  // 128 queries per wave
   const uint32_t ntiles = (uint32_t)((ix->nrows + 63) / 64);
@@ -1523,11 +1525,17 @@ static int linear_search_l1f(ngt_amd_index* ix, SearchCtx* c, LinearArgs& a, hip
   // VGPRs allow them (up to 128: Dp <= 128), two beyond (Dp <= 256 takes 175),
   // fewer where the k-lists (128 k 8 + 256 bytes a wave) fill the CU's LDS first
   uint32_t wpc = std::min<uint32_t>(ix->dp > 128 ? 8 : 16, (uint32_t)(ix->lds_per_cu / (128 * a.k * 8 + 256)));
+  // the wide kernel: what its own VGPR figures allow, its 8 KiB
+  // of pending slots a wave leave the CU's LDS room for more, whatever k
+  if (wide)
+    wpc = std::min<uint32_t>(4 * scan_l1f_wide_waves((int)ix->dp), (uint32_t)(ix->lds_per_cu / kL1fWideLdsBytes));
   wpc = std::max<uint32_t>(4, wpc / 4 * 4);
   uint32_t np = std::max<uint32_t>(1, (uint32_t)ix->cu_count * wpc / mblocks);
   // for tests: at most this many parts, so that a small table still has parts of several tiles
   if (const char* v = ngt_amd::knob("NGT_AMD_SCAN_L1F_PARTS"))
     if (atoi(v) > 0) np = std::min(np, (uint32_t)atoi(v));
+  // the wide kernel: a row's offset in its part takes 16 bits
+  if (wide) np = std::max(np, (ntiles + kL1fWideMaxTiles - 1) / kL1fWideMaxTiles);
   np = std::min(np, ntiles);
   const uint32_t per = (ntiles + np - 1) / np;
   const size_t qwords = (size_t)scan_bytes_chunks((int)ix->dp) * 4;
@@ -1584,7 +1592,13 @@ static int linear_search_l1f(ngt_amd_index* ix, SearchCtx* c, LinearArgs& a, hip
   }
   HIP_OK(c->partial.alloc((size_t)a.nq * m.nparts * a.k));
   m.partial = c->partial.p;
-  HIP_OK(launch_scan_l1f(m, s));
+  if (wide) {
+    const hipError_t e = launch_scan_l1f_wide(m, s);
+    if (e == hipErrorNotSupported) return 1;
+    HIP_OK(e);
+  } else {
+    HIP_OK(launch_scan_l1f(m, s));
+  }
   a.partial = m.partial;
   HIP_OK(launch_linear_merge(a, m.nparts, s));
   // all-NaN queries: the ids in the order linearSearch's heap leaves them (with a radius none passes)
@@ -1593,8 +1607,9 @@ static int linear_search_l1f(ngt_amd_index* ix, SearchCtx* c, LinearArgs& a, hip
     unsigned long long h[2];
     HIP_OK(hipMemcpyAsync(h, d_stats.p, sizeof(h), hipMemcpyDeviceToHost, s));
     HIP_OK(hipStreamSynchronize(s));
-    fprintf(stderr, "scan_l1f: nq %u parts %u rows_per_part %u candidates %llu (%.2f per query and part) tile_queries %llu\n",
-            a.nq, m.nparts, per * 64, h[0], (double)h[0] / ((double)a.nq * m.nparts), h[1]);
+    fprintf(stderr, "%s: nq %u parts %u rows_per_part %u candidates %llu (%.2f per query and part) %s %llu\n",
+            wide ? "scan_l1f_wide" : "scan_l1f", a.nq, m.nparts, per * 64, h[0],
+            (double)h[0] / ((double)a.nq * m.nparts), wide ? "rounds" : "tile_queries", h[1]);
   }
   return 0;
 }
@@ -1737,6 +1752,22 @@ extern "C" int ngt_amd_linear_search_device(ngt_amd_index* ix, const void* d_que
       ix->row_bytes % 16 == 0 && query_bytes % 16 == 0 && (uintptr_t)d_queries % 16 == 0 && ix->nrows > 1) {
     ix->last_scan = 6;
     return linear_search_l1f(ix, c, a, s);
+  }
+  // The same filter with lists of 17 .. 128 results (scan_l1f_wide.hip): the
+  // candidates wait in pending slots, a round recomputes up to 32 of one
+  // query together and sorts them into the list in the partial buffer.
+  // Opt-in for now: only a non-zero NGT_AMD_LINEAR_L1FWIDE, read per call,
+  // takes it; a shape the launcher refuses falls through to the quad kernel.
+  const char* l1fwide_knob = ngt_amd::knob("NGT_AMD_LINEAR_L1FWIDE");
+  if (l1fwide_knob && atoi(l1fwide_knob) != 0 && nq >= 32 && ix->otype == NGT_AMD_OBJECT_FLOAT &&
+      ix->metric == NGT_AMD_DISTANCE_L1 && k >= 17 && k <= 128 && ix->dp <= 256 && ix->dp % 16 == 0 &&
+      ix->dim <= ix->dp && ix->row_bytes % 16 == 0 && query_bytes % 16 == 0 && (uintptr_t)d_queries % 16 == 0 &&
+      ix->nrows > 1) {
+    const int rc = linear_search_l1f(ix, c, a, s, true);
+    if (rc <= 0) {
+      if (rc == 0) ix->last_scan = 10;
+      return rc;
+    }
   }
   // Batches of queries: the query-tiled scan (128 queries per workgroup,
   // packed FMA, scan_kernels.hip) over enough row parts for ~3 workgroups

@@ -566,6 +566,15 @@ hipError_t launch_scan_l1f(const L1fScanArgs& a, hipStream_t s);
 // after the merge, without a radius: the ids of queries with a NaN element in linearSearch's order
 hipError_t launch_scan_l1f_nan(const L1fScanArgs& a, uint32_t* out_ids, uint32_t out_stride, hipStream_t s);
 float scan_l1f_range_value(uint32_t ordered);  // the float of an ordered word of launch_scan_l1f_range
+// The same filter with lists of 1 .. 128 results (scan_l1f_wide.hip): the
+// arguments of launch_scan_l1f, stats[1] counting rounds.  The (query, part)
+// lists are sorted in place in a.partial, the LDS (8 KiB a wave) does not grow
+// with k.  hipErrorNotSupported for a shape outside the above or a part of
+// more than kL1fWideMaxTiles tiles.
+constexpr uint32_t kL1fWideMaxTiles = 1024;  // 64-row tiles of a part: a row's offset in it takes 16 bits
+constexpr uint32_t kL1fWideLdsBytes = 8192;  // a wave's pending slots: 128 queries x 32 slots x 16 bits
+hipError_t launch_scan_l1f_wide(const L1fScanArgs& a, hipStream_t s);
+uint32_t scan_l1f_wide_waves(int dp);  // waves per SIMD the kernel's VGPRs allow, four at the most
 
 // ---- NGTQG (qg_kernels.hip) ------------------------------------------------
 struct QgLutArgs {

@@ -222,7 +222,9 @@ class DeviceIndex(object):
         byte-SAD filter with exact recompute, 7 uint8 Cosine / Angle on the
         int8 matrix cores, 8 uint8 L2 on the int8 matrix cores with lists of
         17 .. 128 results, 9 uint8 L1 / Hamming with lists of 17 .. 128 results
-        and uint8 Jaccard with lists of 1 .. 128 on packed byte-SAD and popcount."""
+        and uint8 Jaccard with lists of 1 .. 128 on packed byte-SAD and popcount,
+        10 float L1 on the byte-SAD filter with exact recompute and lists of
+        17 .. 128 results."""
         return int(self.L.ngt_amd_last_scan_kernel(self.h))
 
     def last_search_lookahead(self):
