@@ -230,7 +230,9 @@ int ngt_amd_last_search_filtered(const ngt_amd_index *index);
  * without an all-zero live row; opt-in for now), 10 float L1 on
  * the byte-SAD filter with exact recompute and lists of 17 .. 128 results
  * (batches of >= 32 queries, padded dimension <= 256; opt-in for now,
- * DESIGN 4a).  The last call on the index wins. */
+ * DESIGN 4a), 11 uint8 L1 / Hamming on rows of 272 .. 1024 padded bytes,
+ * walked in 64-byte pieces (batches of >= 32 queries, k <= 16; opt-in for
+ * now).  The last call on the index wins. */
 int ngt_amd_last_scan_kernel(const ngt_amd_index *index);
 /* The device error word of the launch context of `stream` (created on first
  * use, zeroed on that stream and waited for), read on that stream: the word a

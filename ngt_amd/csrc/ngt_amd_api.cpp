@@ -1374,6 +1374,58 @@ static int linear_search_bytes(ngt_amd_index* ix, SearchCtx* c, LinearArgs& a, h
   return 0;
 }
 
+// uint8 L1 / Hamming batches on rows of 256 < Dp <= 1024 bytes: the work split
+// of linear_search_bytes with the row walked in 64-byte pieces against the
+// sums of a wave's 64 queries (scan_bytes_long.hip).  NGT_AMD_SCAN_WIDE_PARTS
+// caps the parts here too, so that a test's small table still has parts of
+// several tiles.  1: a shape the launcher refused; the caller falls through to
+// the quad kernel.
+static int linear_search_bytes_long(ngt_amd_index* ix, SearchCtx* c, LinearArgs& a, hipStream_t s) {
+  const uint32_t qb = kBytesLongQ;
+  const uint32_t mblocks = (a.nq + qb - 1) / qb;
+  const uint32_t ntiles = (uint32_t)((ix->nrows + 63) / 64);
+  // One resident set of waves over every query block: four waves per SIMD
+  // (the kernel's VGPRs), fewer where a wave's lists and staging fill the
+  // CU's LDS first
+  uint32_t wpc = std::min<uint32_t>(16, (uint32_t)(ix->lds_per_cu / scan_bytes_long_lds_bytes(a.k)));
+  wpc = std::max<uint32_t>(4, wpc / 4 * 4);
+  uint32_t np = std::max<uint32_t>(1, (uint32_t)ix->cu_count * wpc / mblocks);
+  if (const char* v = ngt_amd::knob("NGT_AMD_SCAN_WIDE_PARTS"))
+    if (atoi(v) > 0) np = std::min(np, (uint32_t)atoi(v));
+  np = std::min(np, ntiles);
+  const uint32_t per = (ntiles + np - 1) / np;
+  BytesScanArgs m{};
+  m.rows = ix->rows.p;
+  m.row_bytes = ix->row_bytes;
+  m.nrows = ix->nrows;
+  m.valid = ix->valid.p;
+  m.nq = a.nq;
+  m.k = a.k;
+  m.dp = (int)ix->dp;
+  m.mblocks = mblocks;
+  m.ntiles = ntiles;
+  m.tiles_per_part = per;
+  m.nparts = (ntiles + per - 1) / per;
+  // (radius < 0 || (double)d <= radius) of the quad kernel on d = (float)S:
+  // S <= floor(radius), as a bound on the keys (S << 32 | id)
+  m.key_init = ~0ull;
+  if (!(a.radius < 0.0)) {
+    if (!(a.radius >= 0.0)) m.key_init = 0;  // NaN: no distance passes
+    else if (a.radius < 4.0e9) m.key_init = ((uint64_t)a.radius + 1) << 32;
+  }
+  HIP_OK(c->bq.alloc((size_t)mblocks * scan_bytes_long_pieces(m.dp) * qb * 16));
+  HIP_OK(c->partial.alloc((size_t)a.nq * m.nparts * a.k));
+  m.qpad = c->bq.p;
+  m.partial = c->partial.p;
+  HIP_OK(launch_scan_bytes_long_prep(a.queries, a.query_bytes, a.nq, m.dp, c->bq.p, mblocks, s));
+  const hipError_t e = launch_scan_bytes_long(m, ix->metric, s);
+  if (e == hipErrorNotSupported) return 1;
+  HIP_OK(e);
+  a.partial = m.partial;
+  HIP_OK(launch_linear_merge(a, m.nparts, s));
+  return 0;
+}
+
 // Whether a live row is all zero, found once per version of the rows: against
 // an all-zero query such a row has de = 0 and the comparator's NaN, which the
 // Jaccard scan of scan_bytes_wide.hip does not rank.  -1: error.
@@ -1738,6 +1790,22 @@ extern "C" int ngt_amd_linear_search_device(ngt_amd_index* ix, const void* d_que
     const int rc = linear_search_bytes_wide(ix, c, a, s);
     if (rc <= 0) {
       if (rc == 0) ix->last_scan = 9;
+      return rc;
+    }
+  }
+  // uint8 L1 / Hamming on rows of 256 < Dp <= 1024 bytes, lists of 1 .. 16
+  // (scan_bytes_long.hip): the row in 64-byte pieces against per-query sums in
+  // registers.  Opt-in for now: only a non-zero NGT_AMD_LINEAR_BYTESLONG, read
+  // per call, takes it; a shape the launcher refuses falls through to the
+  // quad kernel.  Rows are read 16 bytes, queries 4 bytes at a time.
+  const char* byteslong_knob = ngt_amd::knob("NGT_AMD_LINEAR_BYTESLONG");
+  if (byteslong_knob && atoi(byteslong_knob) != 0 && nq >= 32 && ix->otype == NGT_AMD_OBJECT_UINT8 &&
+      (ix->metric == NGT_AMD_DISTANCE_L1 || ix->metric == NGT_AMD_DISTANCE_HAMMING) && k <= 16 && ix->dp > 256 &&
+      ix->dp <= 1024 && ix->dp % 16 == 0 && ix->row_bytes % 16 == 0 && query_bytes % 4 == 0 &&
+      (uintptr_t)d_queries % 4 == 0 && ix->nrows > 1) {
+    const int rc = linear_search_bytes_long(ix, c, a, s);
+    if (rc <= 0) {
+      if (rc == 0) ix->last_scan = 11;
       return rc;
     }
   }

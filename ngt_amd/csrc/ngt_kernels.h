@@ -493,6 +493,18 @@ hipError_t launch_scan_bytes_prep(const uint8_t* queries, uint64_t query_bytes, 
                                   uint32_t mblocks, hipStream_t s);
 hipError_t launch_scan_bytes(const BytesScanArgs& a, int metric, hipStream_t s);
 
+// The same scan for rows of 256 < Dp <= 1024 bytes (scan_bytes_long.hip): the
+// row walked in 64-byte pieces against the 64 queries of a wave, k <= 16.
+// BytesScanArgs with mblocks = ceil(nq / 64) and
+// qpad = [mblocks][scan_bytes_long_pieces(dp)][64][16] zero-padded query words.
+constexpr uint32_t kBytesLongQ = 64;             // queries per wave
+uint32_t scan_bytes_long_pieces(int dp);         // 64-byte pieces of a row
+size_t scan_bytes_long_lds_bytes(uint32_t k);    // a wave's lists and staging
+hipError_t launch_scan_bytes_long_prep(const uint8_t* queries, uint64_t query_bytes, uint32_t nq, int dp,
+                                       uint32_t* qpad, uint32_t mblocks, hipStream_t s);
+// metric: L1 or Hamming; hipErrorNotSupported for a shape outside the above
+hipError_t launch_scan_bytes_long(const BytesScanArgs& a, int metric, hipStream_t s);
+
 // uint8 L1 / Hamming / Jaccard exact scan with lists of 1 .. 128 results
 // (scan_bytes_wide.hip): Dp <= 256 a multiple of 16, rows 16-byte aligned.
 // The (query, part) lists are sorted in place in a.partial, the LDS does not

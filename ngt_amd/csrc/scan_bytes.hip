@@ -37,11 +37,9 @@
 
 #include "ngt_device.h"
 #include "ngt_kernels.h"
+#include "scan_bytes_common.h"
 
 namespace ngt_amd {
-
-typedef uint32_t bs_u32x4 __attribute__((ext_vector_type(4)));
-typedef const __attribute__((address_space(4))) uint32_t* bs_const_words;  // read through the scalar cache
 
 constexpr uint32_t kBsQ = 128;  // queries per wave
 
@@ -57,12 +55,6 @@ __global__ void __launch_bounds__(256) ngt_scan_bytes_prep_kernel(const uint8_t*
     if (q < nq && w * 4 < (uint32_t)dp) v = reinterpret_cast<const uint32_t*>(queries + q * query_bytes)[w];
     out[i] = v;
   }
-}
-
-__device__ __forceinline__ uint64_t bs_readlane(uint64_t v, uint32_t l) {
-  const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, (int)l);
-  const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), (int)l);
-  return ((uint64_t)hi << 32) | lo;
 }
 
 template <int M, int NC>
@@ -97,38 +89,6 @@ __global__ void __launch_bounds__(64) ngt_scan_bytes_kernel(BytesScanArgs a) {
     if (a.valid != nullptr) vb = a.valid[rid];
   };
 
-  // Survivors m of query q into its list; S and key are the lanes' values.
-  auto insert = [&](uint32_t q, uint64_t m, uint32_t S, uint64_t key, uint64_t t, uint64_t& thrv) {
-    if ((uint32_t)__popcll(m) > k) {
-      // T = the k-th smallest S of the survivors: the largest T with fewer
-      // than k survivors below it
-      uint32_t T = 0;
-      for (int b = 31 - __builtin_clz(NC * 16 * 255); b >= 0; b--) {
-        const uint32_t cand = T | (1u << b);
-        if ((uint32_t)__popcll(__ballot(S < cand) & m) < k) T = cand;
-      }
-      m &= __ballot(S <= T);
-    }
-    uint64_t* L = lists + q * k;
-    uint64_t e = lane < k ? L[lane] : ~0ull;
-    while (m) {
-      const uint32_t j = (uint32_t)__ffsll((long long)m) - 1;
-      m &= m - 1;
-      const uint64_t kj = bs_readlane(key, j);
-      if (kj >= t) continue;
-      // kj < t <= e[k - 1]: the rank is below k, the k-th entry drops out
-      const uint32_t pos = (uint32_t)__popcll(__ballot(e < kj));
-      const uint32_t ulo = (uint32_t)__shfl_up((int)(uint32_t)e, 1, 64);
-      const uint32_t uhi = (uint32_t)__shfl_up((int)(uint32_t)(e >> 32), 1, 64);
-      const uint64_t up = ((uint64_t)uhi << 32) | ulo;
-      if (lane < k && lane >= pos) e = lane == pos ? kj : up;
-      const uint64_t kth = bs_readlane(e, k - 1);
-      if (kth < t) t = kth;
-    }
-    if (lane < k) L[lane] = e;
-    if (lane == (q & 63)) thrv = t;
-  };
-
   // the loads of tile t + 1 are in flight while tile t is compared
   bs_u32x4 cur[NC], nxt[NC];
   uint32_t vb_nxt = 0;
@@ -159,18 +119,13 @@ __global__ void __launch_bounds__(64) ngt_scan_bytes_kernel(BytesScanArgs a) {
           const uint64_t key = ((uint64_t)S << 32) | id_cur;
           const uint64_t tq = bs_readlane(thr[h], ql);
           const uint64_t m = __ballot(key < tq) & livem;
-          if (m) insert(q, m, S, key, tq, thr[h]);
+          if (m) bs_insert<NC * 16 * 255>(lists, k, lane, q, m, S, key, tq, thr[h]);
         }
       }
     }
   }
   __syncthreads();
-  for (uint32_t i = lane; i < nqb * k; i += 64) {
-    const uint32_t ql = i / k, rr = i - ql * k;
-    const uint64_t e = lists[i];
-    a.partial[((uint64_t)(q0 + ql) * a.nparts + part) * k + rr] =
-        e == ~0ull ? ~0ull : make_key((float)(uint32_t)(e >> 32), (uint32_t)e);
-  }
+  bs_store_lists(lists, nqb, k, lane, q0, a.nparts, part, a.partial);
 }
 
 int scan_bytes_chunks(int dp) {

@@ -224,7 +224,8 @@ class DeviceIndex(object):
         17 .. 128 results, 9 uint8 L1 / Hamming with lists of 17 .. 128 results
         and uint8 Jaccard with lists of 1 .. 128 on packed byte-SAD and popcount,
         10 float L1 on the byte-SAD filter with exact recompute and lists of
-        17 .. 128 results."""
+        17 .. 128 results, 11 uint8 L1 / Hamming on rows of 272 .. 1024 padded
+        bytes walked in 64-byte pieces."""
         return int(self.L.ngt_amd_last_scan_kernel(self.h))
 
     def last_search_lookahead(self):
